@@ -17,7 +17,12 @@ FIELDS_FLOAT = ("lengths", "L", "x", "y", "yaw", "cs")
 
 def golden():
     g = np.load(os.path.join(HERE, "golden", "rs_calc_all_paths.npz"))
-    pts = g["points"]
+    pts, k = [g["points_0"]], 1   # the samples continue in rs_calc_all_paths_points_<k>.npz (make_golden.py)
+    while os.path.exists(os.path.join(HERE, "golden", f"rs_calc_all_paths_points_{k}.npz")):
+        pts.append(np.load(os.path.join(HERE, "golden", f"rs_calc_all_paths_points_{k}.npz"))[f"points_{k}"])
+        k += 1
+    pts = np.concatenate(pts, axis=0)
+    assert pts.shape[0] == int(g["point_offsets"][-1])   # every part is there
     out = {"queries": g["cases"], "path_offsets": g["path_offsets"].astype(np.int64),
            "status": np.zeros(len(g["cases"]), np.int32), "lengths": g["lengths"], "L": g["L"],
            "ctypes": np.array([[SEG[c] for c in s] for s in g["ctypes"]], np.int8).reshape(-1, 5),

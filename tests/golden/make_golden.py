@@ -16,6 +16,7 @@ import numpy as np
 sys.dont_write_bytecode = True
 REF = "/root/reference/path_planner/utils"
 HERE = os.path.dirname(os.path.abspath(__file__))
+RS_POINT_PARTS = 3   # rs_calc_all_paths.npz + rs_calc_all_paths_points_{1,2}.npz (tests/_rs_util.golden joins them)
 
 
 def main():
@@ -44,10 +45,14 @@ def main():
             pts.append(arr)
             ptoff.append(ptoff[-1] + arr.shape[0])
         pathoff.append(len(Ls))
+    # the samples in RS_POINT_PARTS files of equal row counts, so that none is a large file
+    parts = np.array_split(np.concatenate(pts, axis=0), RS_POINT_PARTS, axis=0)
     np.savez_compressed(os.path.join(HERE, "rs_calc_all_paths.npz"),
                         cases=np.array(cases), path_offsets=np.array(pathoff), lengths=np.array(lens),
                         ctypes=np.array(ctyp), L=np.array(Ls), point_offsets=np.array(ptoff),
-                        points=np.concatenate(pts, axis=0))
+                        points_0=parts[0])
+    for k in range(1, RS_POINT_PARTS):
+        np.savez_compressed(os.path.join(HERE, f"rs_calc_all_paths_points_{k}.npz"), **{f"points_{k}": parts[k]})
     # ---- cubic spline: calc_spline_course on random polylines
     sc, sx, sy, soff, out, ooff = [], [], [], [0], [], [0]
     for k in range(40):

@@ -40,7 +40,7 @@ for S in "$@"; do
   case $S in
     tests) run gputest 700 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread
            run smoke 200 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 400 python -u bench.py ;;
+    bench) run bench 400 python -u bench.py --full ;;
     kt) run ktgen 300 python -u bench.py --gen-only --cache /tmp/htp_instcache
         run kt 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${T}_kt -o kt -- python3 bench.py --no-cpu-baseline --cache /tmp/htp_instcache ;;
     pmc) bash tools/gpu_pmc.sh ${T}D --batch 4096 || exit 1
