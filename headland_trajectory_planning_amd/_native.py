@@ -193,7 +193,32 @@ def _declare(lib):
     if hasattr(lib, "htp_mfma_f64_probe"):   # absent from libraries built before it (A/B variants of old kernels)
         lib.htp_mfma_f64_probe.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
         lib.htp_mfma_f64_probe.restype = ctypes.c_int
+    if hasattr(lib, "htp_bk_probe"):   # likewise
+        lib.htp_bk_probe.argtypes = [ctypes.c_void_p] + BK_PROBE_ARGS + [ctypes.c_void_p]
+        lib.htp_bk_probe.restype = ctypes.c_int
     return lib
+
+
+# htp_bk_probe (csrc/bk_probe.h) after the context: variant, n, lane_stride, count, nrhs, then K0, rhs, K, ip, flags,
+# x, x2; the test-only host builds of the same body take exactly these
+BK_PROBE_ARGS = [ctypes.c_int32] * 3 + [ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 7
+BK_SENTINEL = -7.25e300   # pre-fill of the probe's double outputs (ints: -77): what a form leaves untouched stays so
+
+
+def bk_probe_sizes(variant, n):
+    """Doubles per block of htp_bk_probe's input matrix and of its factor (bk_probe.h in_doubles / out_doubles)."""
+    if variant == 6:
+        return 9, 9
+    if variant == 7:
+        return 25, 15
+    return n * (n + 1) // 2, n * (n + 1) // 2
+
+
+def bk_probe_outputs(variant, n, rows, nrhs):
+    """Sentinel-filled host outputs of `rows` blocks: K, ip, flags, x, x2."""
+    _, vo = bk_probe_sizes(variant, n)
+    return (np.full((rows, vo), BK_SENTINEL), np.full((rows, n), -77, np.int32), np.full((rows, 4), -77, np.int32),
+            np.full((rows, nrhs, n), BK_SENTINEL), np.full((rows, nrhs, n), BK_SENTINEL))
 
 
 # correctly rounded libm of the planner cores (csrc/htp_libm.h): function ids of htp_libm_batch_device
@@ -932,6 +957,30 @@ class Context:
             raise RuntimeError(f"[htp] htp_mfma_f64_probe failed: {self.error()}")
         s.synchronize()
         return out.cpu().numpy()
+
+    def bk_probe(self, variant, n, K0, rhs, lane_stride=1, extra_rows=0):
+        """htp_bk_probe over host blocks K0 [count, *] and right-hand sides rhs [count, nrhs, n] -> dict of host
+        arrays K, ip, flags, x, x2.  The outputs are pre-filled with a sentinel and have `extra_rows` rows past
+        `count`, which the kernel's inactive lanes must leave untouched."""
+        import torch
+        if not hasattr(self.lib, "htp_bk_probe"):
+            raise RuntimeError("[htp] this libhtp.so has no htp_bk_probe")
+        dev = torch.device("cuda", self.device)
+        vi, _ = bk_probe_sizes(variant, n)
+        K0 = np.array(K0, dtype=np.float64, order="C")   # copies: torch wants writable arrays
+        rhs = np.array(rhs, dtype=np.float64, order="C")
+        count, nrhs = K0.shape[0], rhs.shape[1]
+        if K0.shape != (count, vi) or rhs.shape != (count, nrhs, n):
+            raise ValueError(f"[htp] bk_probe: K0 must be [count, {vi}] and rhs [count, nrhs, {n}]")
+        tin = [torch.from_numpy(v).to(dev) for v in (K0, rhs)]
+        tout = [torch.from_numpy(v).to(dev) for v in bk_probe_outputs(variant, n, count + extra_rows, nrhs)]
+        s = torch.cuda.current_stream(dev)
+        rc = self.lib.htp_bk_probe(self.ctx, variant, n, lane_stride, count, nrhs, tin[0].data_ptr(),
+                                   tin[1].data_ptr(), *[t.data_ptr() for t in tout], ctypes.c_void_p(s.cuda_stream))
+        if rc != 0:
+            raise RuntimeError(f"[htp] htp_bk_probe failed: {self.error()}")
+        s.synchronize()
+        return dict(zip(("K", "ip", "flags", "x", "x2"), [t.cpu().numpy() for t in tout]))
 
     def solve_points(self, packed):
         """Batched optimizer_points.py solve (host buffers)."""

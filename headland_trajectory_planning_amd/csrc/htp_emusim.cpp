@@ -100,3 +100,14 @@ extern "C" int htp_emusim_obca_points_solve(const htp_obca_points_batch* in, htp
   }
   return 0;
 }
+
+// The small dense factorizations of obca_core.h on caller blocks (bk_probe.h; the arguments of htp_bk_probe,
+// host arrays) with the device build's contraction.  Serial: each block is one lane's work, no wave operations.
+#include "bk_probe.h"
+
+extern "C" int htp_emusim_bk_probe(int32_t variant, int32_t n, int32_t lane_stride, int64_t count, int32_t nrhs,
+                                   const double* K0, const double* rhs, double* K, int32_t* ip, int32_t* flags,
+                                   double* x, double* x2) {
+  std::vector<double> lds(LDS_WAVE_DOUBLES, 0.0);
+  return bkp::run_host<EmuWave>(variant, n, lane_stride, count, nrhs, K0, rhs, K, ip, flags, x, x2, lds.data());
+}

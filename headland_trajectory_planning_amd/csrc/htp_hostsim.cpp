@@ -107,3 +107,20 @@ extern "C" int htp_hostsim_obca_points_solve(const htp_obca_points_batch* in, ht
   }
   return 0;
 }
+
+// The small dense factorizations of obca_core.h on caller blocks (bk_probe.h; the arguments of htp_bk_probe,
+// host arrays), serial build.  Block idx runs as lane idx % 64 of one wave's LDS image.
+#include "bk_probe.h"
+
+extern "C" int htp_hostsim_bk_probe(int32_t variant, int32_t n, int32_t lane_stride, int64_t count, int32_t nrhs,
+                                    const double* K0, const double* rhs, double* K, int32_t* ip, int32_t* flags,
+                                    double* x, double* x2) {
+  std::vector<double> lds(LDS_WAVE_DOUBLES, 0.0);
+  return bkp::run_host<HostLane>(variant, n, lane_stride, count, nrhs, K0, rhs, K, ip, flags, x, x2, lds.data());
+}
+
+// piv_put(w, j, v) and the n slots of the result read back with piv_get
+extern "C" unsigned long long htp_hostsim_bk_piv(unsigned long long w, int32_t j, int32_t v, int32_t n,
+                                                 int32_t* slots) {
+  return bkp::piv_roundtrip(w, j, v, n, slots);
+}

@@ -343,6 +343,10 @@ struct PtBlock {
 template <class T>
 HTP_HD inline T& pk_at(T* K, int r, int c) { return r >= c ? K[r * (r + 1) / 2 + c] : K[c * (c + 1) / 2 + r]; }
 
+// A NaN pivot fails every comparison of the pivot search and used to end in the 2 x 2 branch even at the last row
+// k = n - 1 (imax = k there), which reads K and writes ip one row past the block; with finite entries the last row
+// never gets that far (colmax = 0), so the guard changes no finite result.  A NaN pivot is neither negative nor
+// zero: the block's negative count comes out short, which the inertia test rejects.
 template <class T>
 HTP_HD inline void bk_factor_packed(T* K, int* ip, int n, int& neg, int& zero) {
   const double alpha = 0.6403882032022076;
@@ -362,7 +366,7 @@ HTP_HD inline void bk_factor_packed(T* K, int* ip, int n, int& neg, int& zero) {
         if (j != imax && fabs(pk_at(K, imax, j)) > rowmax) rowmax = fabs(pk_at(K, imax, j));
       if (absakk >= alpha * colmax * (colmax / rowmax)) kp = k;
       else if (fabs(pk_at(K, imax, imax)) >= alpha * rowmax) kp = imax;
-      else { kp = imax; kstep = 2; }
+      else { kp = imax; kstep = k + 1 < n ? 2 : 1; }   // never 2 x 2 at the last row (a NaN pivot, see above)
     }
     const int kk = k + kstep - 1;
     if (kp != kk) {
@@ -532,7 +536,7 @@ HTP_HD HTP_FI inline void bk_factor_simd(T* K, int* ip, int& neg, int& zero) {
         }
       if (absakk >= alpha * colmax * (colmax / rowmax)) kp = kc;
       else if (fabs((double)K[S * (imax * (imax + 1) / 2 + imax)]) >= alpha * rowmax) kp = imax;
-      else { kp = imax; kstep = 2; }
+      else { kp = imax; kstep = kc + 1 < n ? 2 : 1; }
     }
     const int kk = kc + kstep - 1;
     if (act && kp != kk) {
@@ -711,7 +715,7 @@ HTP_HD HTP_FI inline void bk_factor_batch(T* K, int* ip, int& neg, int& zero) {
       for (int j = 0; j < n; ++j) rowmax = (j >= kc && j != imax && rw[j] > rowmax) ? rw[j] : rowmax;
       if (absakk >= alpha * colmax * (colmax / rowmax)) kp = kc;
       else if (dmax >= alpha * rowmax) kp = imax;
-      else { kp = imax; kstep = 2; }
+      else { kp = imax; kstep = kc + 1 < n ? 2 : 1; }
     }
     const int kk = kc + kstep - 1;
     if (act && kp != kk) {                         // the interchanged elements are distinct: load all, then store
@@ -794,7 +798,8 @@ HTP_HD HTP_FI inline void bk_factor_batch(T* K, int* ip, int& neg, int& zero) {
 }
 
 // Bunch-Kaufman pivot vector packed into one 64-bit word (HTP_PIV_V_LDS): entry j in bits [6 j, 6 j + 6) as
-// ip[j] + 32 (|ip[j]| <= n <= 16), so the run-time-indexed reads and writes are shifts on a register, not a
+// ip[j] + 32 (-n <= ip[j] <= n - 1; the n six-bit slots fit the word for n <= 10 only, which bk_factor_batch_p and
+// bk_solve_batch_l assert), so the run-time-indexed reads and writes are shifts on a register, not a
 // private-memory array.  The same integer values as bk_factor_batch's ip.
 HTP_HD HTP_FI inline unsigned long long piv_put(unsigned long long w, int j, int v) {
   return (w & ~(63ull << (6 * j))) | ((unsigned long long)(v + 32) << (6 * j));
@@ -804,6 +809,7 @@ HTP_HD HTP_FI inline int piv_get(unsigned long long w, int j) { return (int)((w 
 // bk_factor_batch with the pivot vector packed (piv_put)
 template <int n, int S, class T>
 HTP_HD HTP_FI inline void bk_factor_batch_p(T* K, unsigned long long& ipw, int& neg, int& zero) {
+  static_assert(6 * n <= 64, "piv_put packs n six-bit pivots into one 64-bit word");
   const double alpha = 0.6403882032022076;
   neg = 0;
   zero = 0;
@@ -839,7 +845,7 @@ HTP_HD HTP_FI inline void bk_factor_batch_p(T* K, unsigned long long& ipw, int& 
       for (int j = 0; j < n; ++j) rowmax = (j >= kc && j != imax && rw[j] > rowmax) ? rw[j] : rowmax;
       if (absakk >= alpha * colmax * (colmax / rowmax)) kp = kc;
       else if (dmax >= alpha * rowmax) kp = imax;
-      else { kp = imax; kstep = 2; }
+      else { kp = imax; kstep = kc + 1 < n ? 2 : 1; }
     }
     const int kk = kc + kstep - 1;
     if (act && kp != kk) {                         // the interchanged elements are distinct: load all, then store
@@ -1009,6 +1015,7 @@ HTP_HD HTP_FI inline void bk_solve_batch(const T* K, const int* ip, double* v) {
 // chains that the compiler folds into private-memory (scratch) accesses.  The same operations on the same values.
 template <int n, int S, class T, class VT>
 HTP_HD HTP_FI inline void bk_solve_batch_l(const T* K, unsigned long long ipw, VT* v) {
+  static_assert(6 * n <= 64, "piv_get reads n six-bit pivots from one 64-bit word");
   int k = 0;
 #pragma unroll 1
   for (int step = 0; step < n; ++step) {          // forward: P, L, D

@@ -539,6 +539,23 @@ int htp_libm_batch_device(htp_ctx* ctx, int32_t fn, const double* x, const doubl
 int htp_mfma_f64_probe(htp_ctx* ctx, const double* A, const double* B, const double* C, double* D, int64_t n,
                        void* stream);
 
+/* The solver's small dense factorizations (csrc/obca_core.h) on `count` caller blocks, one block per lane of
+ * 64-lane workgroups, the LDS laid out as the solver lays out its wave's (csrc/bk_probe.h).  A diagnostic
+ * surface with no reference counterpart (tests/test_gpu_bk.py).  variant: 0 the unpivoted LDL^T of the local
+ * blocks (n 10, 4, 8); 1 bk_factor_packed / bk_solve_packed on a private array (n 4, 8, 10, 18); 2 the same on the
+ * lane-contiguous LDS slice (n 10); 3 bk_factor_simd / bk_solve_simd; 4 bk_factor_batch / bk_solve_batch, and
+ * bk_solve_batch_multi into x2 when nrhs == 4 (3, 4: n 10 with lane_stride 64 or 1, n 18 with lane_stride 1);
+ * 5 bk_factor_batch_p / bk_solve_batch_l (n 10, lane_stride 64 or 1); 6 chol3 / chol3_solve (n = nv = 1, 2, 3);
+ * 7 chol5 / chol5_fwd (x2) / chol5_bwd (n 5).  lane_stride 64: the blocks interleaved in LDS; 1: private arrays.
+ * Device arrays: K0 [count][n (n + 1) / 2] packed lower (6: [count][9], 3 x 3 stride 3; 7: [count][25]);
+ * rhs [count][nrhs][n], nrhs <= 4; K the factor, in K0's layout (7: [count][15] packed); ip [count][n] pivots in
+ * LAPACK dsytf2's convention, 0-based (k, or -(kp + 1) twice for a 2 x 2 pivot); flags [count][4] = negative
+ * pivots, zero pivot, `piv`, Cholesky success (-1 where the form has none); x, x2 [count][nrhs][n].  Rows of
+ * blocks past `count` and outputs a form does not produce are left untouched. */
+int htp_bk_probe(htp_ctx* ctx, int32_t variant, int32_t n, int32_t lane_stride, int64_t count, int32_t nrhs,
+                 const double* K0, const double* rhs, double* K, int32_t* ip, int32_t* flags, double* x, double* x2,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,39 @@ def solve_points_emusim(insts, options=None):
     return res
 
 
+def _bk_probe(fn, variant, n, K0, rhs, lane_stride, extra_rows):
+    fn.argtypes = _native.BK_PROBE_ARGS
+    fn.restype = ctypes.c_int
+    vi, _ = _native.bk_probe_sizes(variant, n)
+    K0 = np.ascontiguousarray(K0, dtype=np.float64)
+    rhs = np.ascontiguousarray(rhs, dtype=np.float64)
+    count, nrhs = K0.shape[0], rhs.shape[1]
+    assert K0.shape == (count, vi) and rhs.shape == (count, nrhs, n), (K0.shape, rhs.shape)
+    outs = _native.bk_probe_outputs(variant, n, count + extra_rows, nrhs)
+    rc = fn(variant, n, lane_stride, count, nrhs, K0.ctypes.data, rhs.ctypes.data, *[o.ctypes.data for o in outs])
+    assert rc == 0, (rc, variant, n, lane_stride)
+    return dict(zip(("K", "ip", "flags", "x", "x2"), outs))
+
+
+def bk_probe_host(variant, n, K0, rhs, lane_stride=1, extra_rows=0):
+    """csrc/bk_probe.h through the serial host build (g++): the arguments and outputs of Context.bk_probe."""
+    return _bk_probe(lib().htp_hostsim_bk_probe, variant, n, K0, rhs, lane_stride, extra_rows)
+
+
+def bk_probe_emusim(variant, n, K0, rhs, lane_stride=1, extra_rows=0):
+    """csrc/bk_probe.h through the contracting host build (clang, the device's contraction)."""
+    return _bk_probe(build_emusim().htp_emusim_bk_probe, variant, n, K0, rhs, lane_stride, extra_rows)
+
+
+def bk_piv_roundtrip(w, j, v, n):
+    """piv_put(w, j, v) -> (the word, its n slots read back with piv_get), serial host build."""
+    f = lib().htp_hostsim_bk_piv
+    f.argtypes = [ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]
+    f.restype = ctypes.c_uint64
+    slots = np.zeros(n, np.int32)
+    return int(f(w, j, v, n, slots.ctypes.data)), slots
+
+
 def build_threadsim():
     """64-thread wavefront simulation (std::barrier per sync) of the same core."""
     os.makedirs(os.path.dirname(TSO), exist_ok=True)
