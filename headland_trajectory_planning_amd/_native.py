@@ -36,6 +36,62 @@ class ObcaResult(ctypes.Structure):
                 ("n_resto", ctypes.c_void_p)]
 
 
+class AuditOpts(ctypes.Structure):  # htp_obca_audit_opts
+    _fields_ = [("substeps", ctypes.c_int32), ("margin_tol", ctypes.c_double), ("dyn_tol", ctypes.c_double),
+                ("bound_tol", ctypes.c_double), ("term_tol", ctypes.c_double)]
+
+
+class AuditResult(ctypes.Structure):  # htp_obca_audit_result
+    _fields_ = [(n, ctypes.c_void_p) for n in ("metrics", "worst", "flags", "stage_clearance")]
+
+
+AUDIT_METRICS = ("clearance", "clearance_node", "dyn_defect", "bound_excess", "init_miss", "term_miss",
+                 "path_length", "total_time")
+AUDIT_FLAGS = {"COLLISION": 1, "MARGIN": 2, "DYNAMICS": 4, "BOUNDS": 8, "TERMINAL": 16, "NONFINITE": 32,
+               "BAD_POLYTOPE": 64}
+AUDIT_MAX_SUBSTEPS = 16
+
+
+def audit_opts(substeps=4, margin_tol=1e-4, dyn_tol=1e-4, bound_tol=1e-4, term_tol=0.0):
+    """htp_obca_audit_opts; the default tolerances are IPOPT's constr_viol_tol, the worst unscaled violation a
+    converged solve may carry (term_tol = 0: the terminal row is soft, so its miss raises no flag)."""
+    return AuditOpts(int(substeps), float(margin_tol), float(dyn_tol), float(bound_tol), float(term_tol))
+
+
+class AuditResults:
+    """Host arrays of one audit: metrics [rows, 8] (AUDIT_METRICS), worst [rows, 4] (stage, substep, obstacle,
+    body), flags [rows] (AUDIT_FLAGS bits), stage_clearance [rows, N] or None."""
+    METRICS = AUDIT_METRICS
+    FLAGS = AUDIT_FLAGS
+
+    def __init__(self, rows, N, stage=True):
+        self.metrics = np.zeros((rows, len(AUDIT_METRICS)))
+        self.worst = np.zeros((rows, 4), dtype=np.int32)
+        self.flags = np.zeros(rows, dtype=np.int32)
+        self.stage_clearance = np.zeros((rows, N)) if stage else None
+
+    def struct(self):
+        r = AuditResult()
+        r.metrics, r.worst, r.flags = self.metrics.ctypes.data, self.worst.ctypes.data, self.flags.ctypes.data
+        r.stage_clearance = None if self.stage_clearance is None else self.stage_clearance.ctypes.data
+        return r
+
+    def metric(self, name):
+        return self.metrics[:, AUDIT_METRICS.index(name)]
+
+    def flag_names(self, k):
+        return [n for n, bit in AUDIT_FLAGS.items() if int(self.flags[k]) & bit]
+
+    def as_dict(self, k):
+        d = {n: float(self.metrics[k, j]) for j, n in enumerate(AUDIT_METRICS)}
+        d["worst"] = dict(zip(("stage", "substep", "obstacle", "body"), (int(v) for v in self.worst[k])))
+        d["flags"] = self.flag_names(k)
+        d["ok"] = int(self.flags[k]) == 0
+        if self.stage_clearance is not None:
+            d["stage_clearance"] = self.stage_clearance[k].copy()
+        return d
+
+
 class RsPaths(ctypes.Structure):
     _fields_ = [("cap_paths", ctypes.c_int64), ("cap_points", ctypes.c_int64), ("n_paths", ctypes.c_int64),
                 ("n_points", ctypes.c_int64)] + [(n, ctypes.c_void_p) for n in (
@@ -92,7 +148,8 @@ EXPORTS = ["htp_obca_sizes", "htp_create", "htp_destroy", "htp_last_error", "htp
            "htp_queue_claimed", "htp_obca_solve_queue_device", "htp_obca_resident_waves",
            "htp_oge_obstacles_batch", "htp_oge_obstacles_batch_device", "htp_oge_last_ms",
            "htp_classic_turn_batch", "htp_classic_turn_batch_device", "htp_classic_last_ms",
-           "htp_orchard_chain_device", "htp_chain_last_ms"]
+           "htp_orchard_chain_device", "htp_chain_last_ms",
+           "htp_obca_audit_batch", "htp_obca_audit_batch_device", "htp_obca_audit_last_ms"]
 
 
 def _declare(lib):
@@ -190,6 +247,14 @@ def _declare(lib):
     lib.htp_libm_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_void_p] * 3 + \
         [ctypes.c_int64, ctypes.c_void_p]
     lib.htp_libm_batch_device.restype = ctypes.c_int
+    if hasattr(lib, "htp_obca_audit_batch"):   # absent from libraries built before it (A/B variants of old kernels)
+        lib.htp_obca_audit_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(ObcaBatch), ctypes.c_void_p,
+                                             ctypes.POINTER(AuditOpts), ctypes.POINTER(AuditResult)]
+        lib.htp_obca_audit_batch.restype = ctypes.c_int
+        lib.htp_obca_audit_batch_device.argtypes = lib.htp_obca_audit_batch.argtypes + [ctypes.c_void_p]
+        lib.htp_obca_audit_batch_device.restype = ctypes.c_int
+        lib.htp_obca_audit_last_ms.argtypes = [ctypes.c_void_p]
+        lib.htp_obca_audit_last_ms.restype = ctypes.c_double
     if hasattr(lib, "htp_mfma_f64_probe"):   # absent from libraries built before it (A/B variants of old kernels)
         lib.htp_mfma_f64_probe.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
         lib.htp_mfma_f64_probe.restype = ctypes.c_int
@@ -1036,6 +1101,36 @@ class Context:
 
     def last_kernel_ms(self):
         return self.lib.htp_last_kernel_ms(self.ctx)
+
+    def audit(self, packed, x, substeps=4, margin_tol=1e-4, dyn_tol=1e-4, bound_tol=1e-4, term_tol=0.0, stage=True):
+        """Geometric audit of decision vectors x [batch, n_var] of `packed` (host buffers) -> AuditResults."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (packed.batch, packed.n_var):
+            raise ValueError(f"[htp] audit: x must be [{packed.batch}, {packed.n_var}], got {x.shape}")
+        res = AuditResults(packed.batch, packed.N, stage)
+        b, r = packed.struct(), res.struct()
+        o = audit_opts(substeps, margin_tol, dyn_tol, bound_tol, term_tol)
+        rc = self.lib.htp_obca_audit_batch(self.ctx, ctypes.byref(b), x.ctypes.data, ctypes.byref(o), ctypes.byref(r))
+        if rc != 0:
+            raise RuntimeError(f"[htp] htp_obca_audit_batch failed: {self.error()}")
+        return res
+
+    def audit_device(self, packed, dev_ptrs, x_ptr, out_ptrs, stream=None, lo=None, hi=None, **opts):
+        """Device-resident audit of `packed` (or of its problems [lo, hi)) on `stream`, not synchronised.  x_ptr:
+        device pointer of the [batch, n_var] rows (e.g. a solve's out x); out_ptrs: device pointers metrics, worst,
+        flags and optionally stage_clearance (torch tensors' data_ptr())."""
+        b = packed.struct(dev_ptrs) if lo is None else packed.chunk_struct(dev_ptrs, lo, hi)
+        r = AuditResult()
+        for k, v in out_ptrs.items():
+            setattr(r, k, v)
+        o = audit_opts(**opts)
+        rc = self.lib.htp_obca_audit_batch_device(self.ctx, ctypes.byref(b), x_ptr, ctypes.byref(o), ctypes.byref(r),
+                                                  stream)
+        if rc != 0:
+            raise RuntimeError(f"[htp] htp_obca_audit_batch_device failed: {self.error()}")
+
+    def audit_last_ms(self):
+        return self.lib.htp_obca_audit_last_ms(self.ctx)
 
     def resident_waves(self, packed):
         v = self.lib.htp_obca_resident_waves(self.ctx, ctypes.byref(packed.struct()))

@@ -6,6 +6,18 @@
 
 #include "htp_common.h"
 
+// A start / end event pair created on first use and released with the context.
+struct htp_event_pair {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  htp_event_pair() = default;
+  htp_event_pair(const htp_event_pair&) = delete;
+  htp_event_pair& operator=(const htp_event_pair&) = delete;
+  ~htp_event_pair() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
 struct htp_ctx {
   using Options = htp::Options;
   using Shape = htp::Shape;
@@ -52,6 +64,8 @@ struct htp_ctx {
   void* yc_ws = nullptr;
   size_t yc_ws_bytes = 0;
   hipEvent_t yc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // trajectory audit (htp_audit.hip)
+  htp_event_pair audit_ev;
 };
 
 static inline int fail(htp_ctx* c, const std::string& m) {

@@ -236,6 +236,24 @@ class OBCAOptimizer(object):
             "slack_opt": x[-5:].copy(), "objective": float(objective),
         }
 
+    def _decision_vector(self, solution: Dict) -> np.ndarray:
+        """X, U and the time scales of a solution dict back in the optimizer's layout; the duals and the slack
+        (which the audit never reads) are zero."""
+        N, ns, nc = self.N, self.n_states, self.n_controls
+        x = np.zeros(self.counts()[0])
+        for k, name in enumerate(("x_opt", "y_opt", "v_opt", "theta_opt", "steer_angle_opt")):
+            x[k:ns * N:ns] = solution[name]
+        o_u = ns * N
+        x[o_u:o_u + nc * (N - 1):nc] = solution["accel_opt"]
+        x[o_u + 1:o_u + nc * (N - 1):nc] = solution["steer_rate_opt"]
+        if self.enable_time_opt:
+            x[-5 - (N - 1):-5] = solution["time_scale_opt"]
+        return x
+
+    def audit(self, solution: Dict, **opts) -> Dict:
+        """Geometric audit of one solution dict (see audit_batch)."""
+        return audit_batch([self], [solution], **opts)[0]
+
     # ------------------------------------------------------------- solve
     def solve(self, max_cpu_time=20, verbose: bool = False) -> Tuple[bool, Dict]:
         """optimizer.py:475-571.  max_cpu_time (IPOPT option, optimizer.py:486) limits
@@ -275,9 +293,28 @@ class OBCAOptimizer(object):
         print("slack cost: ", slack_cost)
 
 
-def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: int = None, max_cpu_time=None):
+def audit_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], device: int = None, **opts) -> List[Dict]:
+    """Audit the trajectories of solution dicts on the device, by geometry alone (no counterpart in the
+    reference, which returns the last iterate of a solve whatever its status, optimizer.py:501-571): signed
+    clearance of the placed bodies against the obstacles at the nodes and at `substeps` poses per interval,
+    dynamics defect, bound excess, start / end miss, path length and time, and the flags judged against
+    margin_tol / dyn_tol / bound_tol / term_tol (_native.Context.audit) -> one dict per solution."""
+    if not optimizers:
+        return []
+    if len(optimizers) != len(solutions):
+        raise ValueError("[OBCA] audit_batch needs one solution per optimizer")
+    dev = optimizers[0].device if device is None else device
+    pk = _native.PackedBatch([o.instance() for o in optimizers])
+    x = np.stack([o._decision_vector(s) for o, s in zip(optimizers, solutions)])
+    res = _context(dev).audit(pk, x, **opts)
+    return [res.as_dict(k) for k in range(pk.batch)]
+
+
+def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: int = None, max_cpu_time=None,
+                audit: Dict = None):
     """Solve many OBCAOptimizer problems in one HIP launch -> [(success, solution)].
-    max_cpu_time (seconds, per problem, device clock; None/<= 0: no limit)."""
+    max_cpu_time (seconds, per problem, device clock; None/<= 0: no limit).  audit: options of audit_batch
+    (a dict, possibly empty); when given, every solution dict gets an "audit" entry."""
     if not optimizers:
         return []
     dev = optimizers[0].device if device is None else device
@@ -296,4 +333,8 @@ def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: 
             print(f"[OBCA] iterations {res.iterations[k]}, factorizations {res.n_factor[k]}, "
                   f"nlp error {res.nlp_error[k]:.3e}")
         out.append((bool(res.status[k] in (0, 1)), o._solution(res.x[k], res.objective[k])))
+    if audit is not None:
+        aud = ctx.audit(pk, res.x, **audit)
+        for k, (_, sol) in enumerate(out):
+            sol["audit"] = aud.as_dict(k)
     return out

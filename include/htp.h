@@ -155,6 +155,67 @@ int htp_obca_points_solve_batch_device(htp_ctx* ctx, const htp_obca_points_batch
                                        void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Audit of solved OBCA trajectories (no reference counterpart for the optimised
+ * trajectory: R/obca_py/optimizer.py:501-571 returns the last iterate of a solve
+ * whatever its status, and its collision rows :386-425 hold MIN_DISTANCE_TO_OBS
+ * only at the N stage nodes, through the duals; the reference's planners check
+ * warm starts on densely sampled poses with check_path_feasibility).  For every
+ * problem of a batch the audit places the body polygons at the poses of the
+ * trajectory and measures, by geometry alone, the signed distance to every
+ * obstacle polygon (Euclidean distance when disjoint, minus the penetration
+ * depth when they intersect); it never reads mu, lambda or the slack.
+ *   Poses: the nodes i = 0..N-1 and, with substeps = S > 1, S-1 poses inside every
+ *   interval, from the NLP's own integrator started at X_i with step h q / S,
+ *   h = dT tau_i (midpoint rule with time_opt, :367-370; Euler otherwise, :372-373).
+ *   `in` is the struct the solve took (init_control / init_mu / init_lambda are
+ *   ignored); x has the solve's n_var stride and optimizer.py's layout; only X, U
+ *   and tau are read.  One wavefront per problem, the whole batch in one launch. */
+#define HTP_AUDIT_MAX_SUBSTEPS 16
+#define HTP_AUDIT_MAX_N 480          /* horizon the kernel's LDS staging holds */
+enum {                               /* double metrics[batch][HTP_AUDIT_NMETRIC] */
+  HTP_AUDIT_CLEARANCE = 0,           /* min signed distance over all poses and (obstacle, body) pairs */
+  HTP_AUDIT_CLEARANCE_NODE,          /* the same over the N nodes only */
+  HTP_AUDIT_DYN_DEFECT,              /* max |X_{i+1} - F(X_i, U_i, tau_i)|, the rows of :364-377 */
+  HTP_AUDIT_BOUND_EXCESS,            /* largest violation of the generate_variables bounds :292-354 (X, U, tau); 0 if none */
+  HTP_AUDIT_INIT_MISS,               /* max |X_0 - init_traj[0]| (the solver's init state, :358) */
+  HTP_AUDIT_TERM_MISS,               /* max |X_{N-1} - init_traj[N-1]| (the solver's end state, :381) */
+  HTP_AUDIT_PATH_LENGTH,             /* sum |v_i| h_i */
+  HTP_AUDIT_TOTAL_TIME,              /* sum h_i */
+  HTP_AUDIT_NMETRIC
+};
+enum {                               /* int32 flags[batch], judged against the caller's tolerances */
+  HTP_AUDIT_COLLISION = 1,           /* clearance < 0 */
+  HTP_AUDIT_MARGIN = 2,              /* clearance < params[HTP_P_DMIN] - margin_tol */
+  HTP_AUDIT_DYNAMICS = 4,            /* defect > dyn_tol */
+  HTP_AUDIT_BOUNDS = 8,              /* excess > bound_tol */
+  HTP_AUDIT_TERMINAL = 16,           /* term_tol > 0 and the terminal miss exceeds it */
+  HTP_AUDIT_NONFINITE = 32,          /* a non-finite double among those read: metrics NaN, worst -1, no other flag */
+  HTP_AUDIT_BAD_POLYTOPE = 64        /* an empty or unbounded obstacle or body: clearance metrics NaN, worst -1 */
+};
+typedef struct {
+  int32_t substeps;                  /* 1 (nodes only) .. HTP_AUDIT_MAX_SUBSTEPS */
+  double margin_tol, dyn_tol, bound_tol, term_tol;   /* >= 0; term_tol = 0 switches HTP_AUDIT_TERMINAL off */
+} htp_obca_audit_opts;
+typedef struct {
+  double* metrics;          /* [batch][HTP_AUDIT_NMETRIC] */
+  int32_t* worst;           /* [batch][4] stage, substep, obstacle, body of HTP_AUDIT_CLEARANCE; ties go to the
+                               lowest (stage, substep, obstacle, body) */
+  int32_t* flags;           /* [batch] HTP_AUDIT_* bits */
+  double* stage_clearance;  /* nullable [batch][N]: min over substeps and pairs for node i and the interval it starts */
+} htp_obca_audit_result;
+/* API errors (-1 with a message, nothing launched): a null argument, N < 2 or > HTP_AUDIT_MAX_N, substeps
+ * outside 1..HTP_AUDIT_MAX_SUBSTEPS, an edge count outside 3..8, a negative tolerance.  batch == 0 returns 0. */
+/* host pointers, synchronous */
+int htp_obca_audit_batch(htp_ctx* ctx, const htp_obca_batch* in, const double* x, const htp_obca_audit_opts* opts,
+                         htp_obca_audit_result* out);
+/* device pointers, enqueued on `stream`, not synchronised: behind htp_obca_solve_batch_device on the same
+ * stream it audits that solve's out->x without a host round trip */
+int htp_obca_audit_batch_device(htp_ctx* ctx, const htp_obca_batch* in, const double* x,
+                                const htp_obca_audit_opts* opts, htp_obca_audit_result* out, void* stream);
+/* duration (ms) of the last audit kernel (hipEvents on its stream) */
+double htp_obca_audit_last_ms(htp_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * Warm start -> OBCA initial guess (R/obca_py/util.py get_init_ref_path :62-113
  * with cubic_spline.calc_spline_course :92-112): split at gear changes,
  * re-spline every segment over arc length at ds, v = gear * desired_v,
