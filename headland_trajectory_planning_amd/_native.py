@@ -92,6 +92,77 @@ class AuditResults:
         return d
 
 
+class TimelineOpts(ctypes.Structure):  # htp_obca_timeline_opts
+    _fields_ = [("dt", ctypes.c_double), ("cap", ctypes.c_int32)]
+
+
+class TimelineResult(ctypes.Structure):  # htp_obca_timeline_result
+    _fields_ = [(n, ctypes.c_void_p) for n in ("rows", "stage", "count", "flags", "duration")]
+
+
+TIMELINE_COLUMNS = ("t", "x", "y", "v", "theta", "steer", "accel", "steer_rate", "curvature", "arc")
+TIMELINE_FLAGS = {"TRUNCATED": 1, "NONFINITE": 2, "BAD_TIME": 4}
+TIMELINE_MAX_N = 480
+
+
+def timeline_opts(dt, cap):
+    return TimelineOpts(float(dt), int(cap))
+
+
+def timeline_cap(packed, x, dt):
+    """Rows of storage that hold every problem of x [batch, n_var] at period dt: the longest duration's row count
+    plus the quotient's rounding (problems the sampler rejects need none); at least 2."""
+    N = packed.N
+    h = packed.params[:, P_DT:P_DT + 1] * (x[:, packed.n_var - 5 - (N - 1):packed.n_var - 5] if packed.time_opt
+                                            else np.ones((packed.batch, N - 1)))
+    with np.errstate(all="ignore"):
+        q = np.cumsum(h, axis=1)[:, -1] / float(dt)
+    q = q[np.isfinite(q) & (q < 2.0 ** 30) & np.all(h > 0, axis=1)]
+    return max(2, int(np.floor(q.max())) + 3) if q.size else 2
+
+
+class TimelineResults:
+    """Host arrays of one timeline: data [rows, cap, 10] (TIMELINE_COLUMNS), stage [rows, cap] or None, count
+    [rows] (rows needed), flags [rows] (TIMELINE_FLAGS bits), duration [rows]."""
+    COLUMNS = TIMELINE_COLUMNS
+    FLAGS = TIMELINE_FLAGS
+
+    def __init__(self, rows, cap, stage=True):
+        self.cap = int(cap)
+        self.data = np.zeros((rows, self.cap, len(TIMELINE_COLUMNS)))
+        self.stage = np.zeros((rows, self.cap), dtype=np.int32) if stage else None
+        self.count = np.zeros(rows, dtype=np.int32)
+        self.flags = np.zeros(rows, dtype=np.int32)
+        self.duration = np.zeros(rows)
+
+    def struct(self):
+        r = TimelineResult()
+        r.rows, r.count, r.flags = self.data.ctypes.data, self.count.ctypes.data, self.flags.ctypes.data
+        r.duration = self.duration.ctypes.data
+        r.stage = None if self.stage is None else self.stage.ctypes.data
+        return r
+
+    def valid(self, k):
+        return min(int(self.count[k]), self.cap)
+
+    def flag_names(self, k):
+        return [n for n, bit in TIMELINE_FLAGS.items() if int(self.flags[k]) & bit]
+
+    def rows(self, k):
+        """The written rows of problem k: a dict of the named column arrays, plus "stage" where it was asked for."""
+        n = self.valid(k)
+        d = {name: self.data[k, :n, j].copy() for j, name in enumerate(TIMELINE_COLUMNS)}
+        if self.stage is not None:
+            d["stage"] = self.stage[k, :n].copy()
+        return d
+
+    def as_dict(self, k):
+        d = self.rows(k)
+        d["duration"] = float(self.duration[k])
+        d["flags"] = self.flag_names(k)
+        return d
+
+
 class RsPaths(ctypes.Structure):
     _fields_ = [("cap_paths", ctypes.c_int64), ("cap_points", ctypes.c_int64), ("n_paths", ctypes.c_int64),
                 ("n_points", ctypes.c_int64)] + [(n, ctypes.c_void_p) for n in (
@@ -149,7 +220,8 @@ EXPORTS = ["htp_obca_sizes", "htp_create", "htp_destroy", "htp_last_error", "htp
            "htp_oge_obstacles_batch", "htp_oge_obstacles_batch_device", "htp_oge_last_ms",
            "htp_classic_turn_batch", "htp_classic_turn_batch_device", "htp_classic_last_ms",
            "htp_orchard_chain_device", "htp_chain_last_ms",
-           "htp_obca_audit_batch", "htp_obca_audit_batch_device", "htp_obca_audit_last_ms"]
+           "htp_obca_audit_batch", "htp_obca_audit_batch_device", "htp_obca_audit_last_ms",
+           "htp_obca_timeline_batch", "htp_obca_timeline_batch_device", "htp_obca_timeline_last_ms"]
 
 
 def _declare(lib):
@@ -255,6 +327,14 @@ def _declare(lib):
         lib.htp_obca_audit_batch_device.restype = ctypes.c_int
         lib.htp_obca_audit_last_ms.argtypes = [ctypes.c_void_p]
         lib.htp_obca_audit_last_ms.restype = ctypes.c_double
+    if hasattr(lib, "htp_obca_timeline_batch"):   # likewise
+        lib.htp_obca_timeline_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(ObcaBatch), ctypes.c_void_p,
+                                                ctypes.POINTER(TimelineOpts), ctypes.POINTER(TimelineResult)]
+        lib.htp_obca_timeline_batch.restype = ctypes.c_int
+        lib.htp_obca_timeline_batch_device.argtypes = lib.htp_obca_timeline_batch.argtypes + [ctypes.c_void_p]
+        lib.htp_obca_timeline_batch_device.restype = ctypes.c_int
+        lib.htp_obca_timeline_last_ms.argtypes = [ctypes.c_void_p]
+        lib.htp_obca_timeline_last_ms.restype = ctypes.c_double
     if hasattr(lib, "htp_mfma_f64_probe"):   # absent from libraries built before it (A/B variants of old kernels)
         lib.htp_mfma_f64_probe.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
         lib.htp_mfma_f64_probe.restype = ctypes.c_int
@@ -1131,6 +1211,43 @@ class Context:
 
     def audit_last_ms(self):
         return self.lib.htp_obca_audit_last_ms(self.ctx)
+
+    def timeline(self, packed, x, dt, cap=None, stage=True):
+        """Uniform-time sampling of decision vectors x [batch, n_var] of `packed` at period dt (host buffers) ->
+        TimelineResults.  cap: rows of storage per problem; None derives it from x (timeline_cap), so that no
+        problem is truncated."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (packed.batch, packed.n_var):
+            raise ValueError(f"[htp] timeline: x must be [{packed.batch}, {packed.n_var}], got {x.shape}")
+        if cap is None:
+            if not (np.isfinite(dt) and dt > 0):
+                raise ValueError(f"[htp] timeline: dt must be finite and > 0, got {dt}")
+            cap = timeline_cap(packed, x, dt)
+        res = TimelineResults(packed.batch, cap, stage)
+        b, r = packed.struct(), res.struct()
+        o = timeline_opts(dt, cap)
+        rc = self.lib.htp_obca_timeline_batch(self.ctx, ctypes.byref(b), x.ctypes.data, ctypes.byref(o),
+                                              ctypes.byref(r))
+        if rc != 0:
+            raise RuntimeError(f"[htp] htp_obca_timeline_batch failed: {self.error()}")
+        return res
+
+    def timeline_device(self, packed, dev_ptrs, x_ptr, out_ptrs, dt, cap, stream=None, lo=None, hi=None):
+        """Device-resident timeline of `packed` (or of its problems [lo, hi)) on `stream`, not synchronised.
+        x_ptr: device pointer of the [batch, n_var] rows (e.g. a solve's out x); out_ptrs: device pointers rows
+        [batch, cap, 10], count, flags and optionally stage [batch, cap] and duration (torch tensors' data_ptr())."""
+        b = packed.struct(dev_ptrs) if lo is None else packed.chunk_struct(dev_ptrs, lo, hi)
+        r = TimelineResult()
+        for k, v in out_ptrs.items():
+            setattr(r, k, v)
+        o = timeline_opts(dt, cap)
+        rc = self.lib.htp_obca_timeline_batch_device(self.ctx, ctypes.byref(b), x_ptr, ctypes.byref(o),
+                                                     ctypes.byref(r), stream)
+        if rc != 0:
+            raise RuntimeError(f"[htp] htp_obca_timeline_batch_device failed: {self.error()}")
+
+    def timeline_last_ms(self):
+        return self.lib.htp_obca_timeline_last_ms(self.ctx)
 
     def resident_waves(self, packed):
         v = self.lib.htp_obca_resident_waves(self.ctx, ctypes.byref(packed.struct()))

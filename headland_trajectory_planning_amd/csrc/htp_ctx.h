@@ -66,6 +66,8 @@ struct htp_ctx {
   hipEvent_t yc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   // trajectory audit (htp_audit.hip)
   htp_event_pair audit_ev;
+  // trajectory timeline (htp_timeline.hip)
+  htp_event_pair timeline_ev;
 };
 
 static inline int fail(htp_ctx* c, const std::string& m) {

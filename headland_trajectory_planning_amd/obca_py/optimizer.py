@@ -254,6 +254,10 @@ class OBCAOptimizer(object):
         """Geometric audit of one solution dict (see audit_batch)."""
         return audit_batch([self], [solution], **opts)[0]
 
+    def timeline(self, solution: Dict, dt: float) -> Dict:
+        """One solution dict sampled every dt seconds (see timeline_batch)."""
+        return timeline_batch([self], [solution], dt)[0]
+
     # ------------------------------------------------------------- solve
     def solve(self, max_cpu_time=20, verbose: bool = False) -> Tuple[bool, Dict]:
         """optimizer.py:475-571.  max_cpu_time (IPOPT option, optimizer.py:486) limits
@@ -310,11 +314,30 @@ def audit_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], device: 
     return [res.as_dict(k) for k in range(pk.batch)]
 
 
+def timeline_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], dt: float, device: int = None) -> List[Dict]:
+    """Sample the trajectories of solution dicts on the device at the fixed period dt (no counterpart in the
+    reference, which returns the nodes of the NLP's grid, spaced dT * time_scale_opt[i]): rows at k * dt from
+    the NLP's own integrator started at the node before each sample, then one row at the stored last node
+    (_native.Context.timeline) -> one dict per solution with the arrays t, x, y, v, theta, steer, accel,
+    steer_rate, curvature, arc and stage, the duration and the flag names.  Between the end of an interval and
+    the next node the rows step by that interval's dynamics defect (audit "dyn_defect")."""
+    if not optimizers:
+        return []
+    if len(optimizers) != len(solutions):
+        raise ValueError("[OBCA] timeline_batch needs one solution per optimizer")
+    dev = optimizers[0].device if device is None else device
+    pk = _native.PackedBatch([o.instance() for o in optimizers])
+    x = np.stack([o._decision_vector(s) for o, s in zip(optimizers, solutions)])
+    res = _context(dev).timeline(pk, x, dt)
+    return [res.as_dict(k) for k in range(pk.batch)]
+
+
 def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: int = None, max_cpu_time=None,
-                audit: Dict = None):
+                audit: Dict = None, timeline: Dict = None):
     """Solve many OBCAOptimizer problems in one HIP launch -> [(success, solution)].
     max_cpu_time (seconds, per problem, device clock; None/<= 0: no limit).  audit: options of audit_batch
-    (a dict, possibly empty); when given, every solution dict gets an "audit" entry."""
+    (a dict, possibly empty); when given, every solution dict gets an "audit" entry.  timeline: dict(dt=...);
+    when given, every solution dict gets a "timeline" entry (see timeline_batch)."""
     if not optimizers:
         return []
     dev = optimizers[0].device if device is None else device
@@ -337,4 +360,8 @@ def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: 
         aud = ctx.audit(pk, res.x, **audit)
         for k, (_, sol) in enumerate(out):
             sol["audit"] = aud.as_dict(k)
+    if timeline is not None:
+        tml = ctx.timeline(pk, res.x, **timeline)
+        for k, (_, sol) in enumerate(out):
+            sol["timeline"] = tml.as_dict(k)
     return out

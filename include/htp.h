@@ -216,6 +216,55 @@ int htp_obca_audit_batch_device(htp_ctx* ctx, const htp_obca_batch* in, const do
 double htp_obca_audit_last_ms(htp_ctx* ctx);
 
 /* ---------------------------------------------------------------------------
+ * Uniform-time sampling of solved OBCA trajectories (no reference counterpart:
+ * R/obca_py/optimizer.py:501-571 returns the N nodes of the NLP's own grid, whose
+ * spacing h_i = dT tau_i differs per interval with time optimisation, :235).  For
+ * every problem of a batch the sampler returns the trajectory at the fixed period
+ * dt, by the NLP's own integrator (midpoint rule with time_opt, :367-370; Euler
+ * otherwise, :372-373) started at the node that opens the interval of each sample.
+ *   Node times t_0 = 0, t_{i+1} = t_i + h_i and node arc lengths A_0 = 0,
+ *   A_{i+1} = A_i + |v_i| h_i are serial left-to-right sums (the order of
+ *   HTP_AUDIT_TOTAL_TIME and HTP_AUDIT_PATH_LENGTH); T = t_{N-1}.
+ *   Regular rows: k = 0, 1, .. while k dt < T, at s = k dt (a product, never
+ *   accumulated); interval i = the largest i in 0..N-2 with t_i <= s; state =
+ *   step(X_i, U_i, s - t_i); arc = A_i + |v_i| (s - t_i).  Then exactly one final
+ *   row: the stored node X_{N-1} with U_{N-2}, t = T, arc = A_{N-1}, stage N-1.
+ *   The end of interval i and node i+1 differ by the solve's dynamics defect
+ *   (HTP_AUDIT_DYN_DEFECT); the sampler does not hide that step.
+ *   `in` is the struct the solve took; only X, U and tau of x and the dT and
+ *   wheelbase parameters are read.  One wavefront per problem, one launch. */
+#define HTP_TIMELINE_NCOL 10         /* t, x, y, v, theta, steer, accel, steer_rate, curvature, arc */
+#define HTP_TIMELINE_MAX_N HTP_AUDIT_MAX_N
+enum {                               /* int32 flags[batch] */
+  HTP_TIMELINE_TRUNCATED = 1,        /* rows needed > cap: the first cap rows are written (possibly without the
+                                        final row); count still holds the rows needed */
+  HTP_TIMELINE_NONFINITE = 2,        /* a non-finite double among those read: count 0, no row written, no other flag */
+  HTP_TIMELINE_BAD_TIME = 4          /* some h_i is not > 0, or T / dt >= 2^30: count 0, no row written */
+};
+typedef struct {
+  double dt;                         /* output period, finite and > 0 */
+  int32_t cap;                       /* rows of storage per problem, >= 2 */
+} htp_obca_timeline_opts;
+typedef struct {
+  double* rows;             /* [batch][cap][HTP_TIMELINE_NCOL]; rows at or beyond min(count, cap) are never written */
+  int32_t* stage;           /* nullable [batch][cap]: the interval i of a regular row, N-1 for the final row */
+  int32_t* count;           /* [batch] rows needed = regular rows + 1 */
+  int32_t* flags;           /* [batch] HTP_TIMELINE_* bits */
+  double* duration;         /* nullable [batch] T; NaN where the h_i are non-finite or not all > 0 */
+} htp_obca_timeline_result;
+/* API errors (-1 with a "[timeline]" message, nothing launched): a null required argument, N < 2 or
+ * > HTP_TIMELINE_MAX_N, dt not finite or <= 0, cap < 2, an edge count outside 3..8.  batch == 0 returns 0. */
+/* host pointers, synchronous; only [X | U | tau] of every x row is uploaded */
+int htp_obca_timeline_batch(htp_ctx* ctx, const htp_obca_batch* in, const double* x,
+                            const htp_obca_timeline_opts* opts, htp_obca_timeline_result* out);
+/* device pointers, enqueued on `stream`, not synchronised: behind htp_obca_solve_batch_device (and the audit)
+ * on the same stream it samples that solve's out->x without a host round trip */
+int htp_obca_timeline_batch_device(htp_ctx* ctx, const htp_obca_batch* in, const double* x,
+                                   const htp_obca_timeline_opts* opts, htp_obca_timeline_result* out, void* stream);
+/* duration (ms) of the last timeline kernel (hipEvents on its stream) */
+double htp_obca_timeline_last_ms(htp_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * Warm start -> OBCA initial guess (R/obca_py/util.py get_init_ref_path :62-113
  * with cubic_spline.calc_spline_course :92-112): split at gear changes,
  * re-spline every segment over arc length at ds, v = gear * desired_v,
