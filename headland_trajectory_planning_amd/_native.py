@@ -163,6 +163,119 @@ class TimelineResults:
         return d
 
 
+class RepairOpts(ctypes.Structure):  # htp_obca_repair_opts
+    _fields_ = [("rounds", ctypes.c_int32), ("pad", ctypes.c_double), ("max_raise", ctypes.c_double),
+                ("audit", AuditOpts)]
+
+
+class RepairState(ctypes.Structure):  # htp_obca_repair_state
+    _fields_ = [(n, ctypes.c_void_p) for n in ("state", "rounds_used", "extra_iterations", "dmin_used")]
+
+
+class RepairSlots(ctypes.Structure):  # htp_obca_repair_slots
+    _fields_ = [("cap", ctypes.c_int32)] + [(n, ctypes.c_void_p) for n in (
+        "count", "index", "adopted", "traj", "obs_A", "obs_b", "body_G", "body_g", "params", "params_audit",
+        "init_control", "init_mu", "init_lambda")]
+
+
+class RepairReport(ctypes.Structure):  # htp_obca_repair_report
+    _fields_ = [("state", RepairState), ("round_counts", ctypes.c_void_p)]
+
+
+REPAIR_STATES = {"CANDIDATE": 1, "IMPROVED": 2, "REPAIRED": 4, "RESOLVE_FAILED": 8, "GAVE_UP": 16}
+REPAIR_MAX_ROUNDS = 8
+REPAIR_STATE_ARRAYS = ("state", "rounds_used", "extra_iterations", "dmin_used")
+REPAIR_SLOT_ARRAYS = ("traj", "obs_A", "obs_b", "body_G", "body_g", "params", "params_audit", "init_control",
+                      "init_mu", "init_lambda")
+
+
+def repair_opts(rounds=3, pad=0.01, max_raise=0.5, **audit):
+    """htp_obca_repair_opts: 3 rounds, 1 cm on top of every raise, at most 0.5 m above the original margin
+    (design choices, not tuned values) and the audit_opts of every audit."""
+    return RepairOpts(int(rounds), float(pad), float(max_raise), audit_opts(**audit))
+
+
+def _struct_of(cls, ptrs, **scalars):
+    s = cls()
+    for k, v in ptrs.items():
+        setattr(s, k, v)
+    for k, v in scalars.items():
+        setattr(s, k, v)
+    return s
+
+
+class RepairStates:
+    """Host arrays of the per-problem repair state; fresh = all zero (dmin_used counts only where rounds_used > 0)."""
+
+    def __init__(self, batch):
+        self.state = np.zeros(batch, dtype=np.int32)
+        self.rounds_used = np.zeros(batch, dtype=np.int32)
+        self.extra_iterations = np.zeros(batch, dtype=np.int32)
+        self.dmin_used = np.zeros(batch)
+
+    def struct(self):
+        return _struct_of(RepairState, {n: getattr(self, n).ctypes.data for n in REPAIR_STATE_ARRAYS})
+
+    def state_names(self, k):
+        return [n for n, bit in REPAIR_STATES.items() if int(self.state[k]) & bit]
+
+
+class RepairSlotArrays:
+    """Host arrays of `cap` slots of a re-solve batch shaped like `packed` (htp_obca_repair_slots)."""
+
+    def __init__(self, packed, cap, fill=0.0, ifill=0):
+        self.shape_of = packed
+        self.cap = int(cap)
+        N = packed.N
+        TEo, TEb = int(packed.obs_edges.sum()), int(packed.body_edges.sum())
+        self.count = np.full(1, ifill, dtype=np.int32)
+        self.index = np.full(self.cap, ifill, dtype=np.int32)
+        self.adopted = np.full(self.cap, ifill, dtype=np.int32)
+        dims = dict(traj=(N, 5), obs_A=(TEo, 2), obs_b=(TEo,), body_G=(TEb, 2), body_g=(TEb,), params=(NPARAM,),
+                    params_audit=(NPARAM,), init_control=(N - 1, 2), init_mu=(N, packed.mu_count),
+                    init_lambda=(N, packed.lam_count))
+        for n in REPAIR_SLOT_ARRAYS:
+            setattr(self, n, np.full((self.cap,) + dims[n], fill))
+
+    def struct(self):
+        ptrs = {n: getattr(self, n).ctypes.data for n in ("count", "index", "adopted") + REPAIR_SLOT_ARRAYS}
+        return _struct_of(RepairSlots, ptrs, cap=self.cap)
+
+    def used(self):
+        return min(int(self.count[0]), self.cap)
+
+    def packed(self, audit=False):
+        """The written slots as a PackedBatch: what a solve takes, or (audit) the same judged by params_audit."""
+        pk = PackedBatch.__new__(PackedBatch)
+        pk.__dict__.update(self.shape_of.__dict__)
+        pk.batch = self.used()
+        for n in PackedBatch.INPUTS:
+            setattr(pk, n, getattr(self, n)[:pk.batch])
+        if audit:
+            pk.params = self.params_audit[:pk.batch]
+        return pk
+
+
+class RepairReports(RepairStates):
+    """Host arrays of one repair loop: the per-problem state and round_counts [8, 3] (selected, adopted, clean)."""
+
+    def __init__(self, batch):
+        super().__init__(batch)
+        self.round_counts = np.zeros((REPAIR_MAX_ROUNDS, 3), dtype=np.int32)
+
+    def report_struct(self):
+        r = RepairReport()
+        r.state = self.struct()
+        r.round_counts = self.round_counts.ctypes.data
+        return r
+
+    def as_dict(self, k, min_dist):
+        """`min_dist`: the problem's original margin, reported where no re-solve was merged."""
+        return {"state": self.state_names(k), "rounds": int(self.rounds_used[k]),
+                "min_dist_used": float(self.dmin_used[k]) if self.rounds_used[k] > 0 else float(min_dist),
+                "extra_iterations": int(self.extra_iterations[k])}
+
+
 class RsPaths(ctypes.Structure):
     _fields_ = [("cap_paths", ctypes.c_int64), ("cap_points", ctypes.c_int64), ("n_paths", ctypes.c_int64),
                 ("n_points", ctypes.c_int64)] + [(n, ctypes.c_void_p) for n in (
@@ -221,7 +334,10 @@ EXPORTS = ["htp_obca_sizes", "htp_create", "htp_destroy", "htp_last_error", "htp
            "htp_classic_turn_batch", "htp_classic_turn_batch_device", "htp_classic_last_ms",
            "htp_orchard_chain_device", "htp_chain_last_ms",
            "htp_obca_audit_batch", "htp_obca_audit_batch_device", "htp_obca_audit_last_ms",
-           "htp_obca_timeline_batch", "htp_obca_timeline_batch_device", "htp_obca_timeline_last_ms"]
+           "htp_obca_timeline_batch", "htp_obca_timeline_batch_device", "htp_obca_timeline_last_ms",
+           "htp_obca_repair_pack_batch", "htp_obca_repair_pack_batch_device", "htp_obca_repair_merge_batch",
+           "htp_obca_repair_merge_batch_device", "htp_obca_repair_batch", "htp_obca_repair_batch_device",
+           "htp_obca_repair_last_ms"]
 
 
 def _declare(lib):
@@ -335,6 +451,23 @@ def _declare(lib):
         lib.htp_obca_timeline_batch_device.restype = ctypes.c_int
         lib.htp_obca_timeline_last_ms.argtypes = [ctypes.c_void_p]
         lib.htp_obca_timeline_last_ms.restype = ctypes.c_double
+    if hasattr(lib, "htp_obca_repair_batch"):   # likewise
+        P = ctypes.POINTER
+        lib.htp_obca_repair_pack_batch.argtypes = [ctypes.c_void_p, P(ObcaBatch), P(ObcaResult), P(AuditResult),
+                                                   P(RepairOpts), P(RepairState), P(RepairSlots)]
+        lib.htp_obca_repair_merge_batch.argtypes = [ctypes.c_void_p, P(ObcaBatch), P(RepairSlots), P(ObcaResult),
+                                                    P(AuditResult), P(ObcaResult), P(AuditResult), P(RepairState),
+                                                    ctypes.c_void_p]
+        lib.htp_obca_repair_batch.argtypes = [ctypes.c_void_p, P(ObcaBatch), P(ObcaResult), P(RepairOpts),
+                                              P(AuditResult), P(RepairReport)]
+        for n in ("pack_batch", "merge_batch", "batch"):
+            f = getattr(lib, "htp_obca_repair_" + n)
+            f.restype = ctypes.c_int
+            g = getattr(lib, "htp_obca_repair_" + n + "_device")
+            g.argtypes = f.argtypes + [ctypes.c_void_p]
+            g.restype = ctypes.c_int
+        lib.htp_obca_repair_last_ms.argtypes = [ctypes.c_void_p, _dp, _dp]
+        lib.htp_obca_repair_last_ms.restype = ctypes.c_int
     if hasattr(lib, "htp_mfma_f64_probe"):   # absent from libraries built before it (A/B variants of old kernels)
         lib.htp_mfma_f64_probe.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
         lib.htp_mfma_f64_probe.restype = ctypes.c_int
@@ -1248,6 +1381,76 @@ class Context:
 
     def timeline_last_ms(self):
         return self.lib.htp_obca_timeline_last_ms(self.ctx)
+
+    def _repair_call(self, name, *args):
+        if getattr(self.lib, name)(self.ctx, *args) != 0:
+            raise RuntimeError(f"[htp] {name} failed: {self.error()}")
+
+    def repair_pack(self, packed, res, aud, states, slots, pad=0.01, max_raise=0.5):
+        """The pack step over host arrays: HostResults `res` and AuditResults `aud` of `packed`, RepairStates
+        `states` (updated) and RepairSlotArrays `slots` (written) -> the number of candidates packed."""
+        b, r, a, o = packed.struct(), res.struct(), aud.struct(), repair_opts(pad=pad, max_raise=max_raise)
+        s, sl = states.struct(), slots.struct()
+        self._repair_call("htp_obca_repair_pack_batch", ctypes.byref(b), ctypes.byref(r), ctypes.byref(a),
+                          ctypes.byref(o), ctypes.byref(s), ctypes.byref(sl))
+        return int(slots.count[0])
+
+    def repair_merge(self, packed, slots, re, re_aud, res, aud, states, tally=None):
+        """The merge step over host arrays: the re-solve `re` / `re_aud` of the packed slots into `res`, `aud` and
+        `states` (all updated in place); tally: int32 [3] or None."""
+        b, sl, r1, a1, r0, a0, s = (v.struct() for v in (packed, slots, re, re_aud, res, aud, states))
+        self._repair_call("htp_obca_repair_merge_batch", ctypes.byref(b), ctypes.byref(sl), ctypes.byref(r1),
+                          ctypes.byref(a1), ctypes.byref(r0), ctypes.byref(a0), ctypes.byref(s),
+                          None if tally is None else tally.ctypes.data)
+
+    def repair_pack_device(self, packed, dev_ptrs, out_ptrs, audit_ptrs, state_ptrs, slot_ptrs, cap, pad=0.01,
+                           max_raise=0.5, stream=None):
+        """Device-resident pack on `stream`, not synchronised.  Every *_ptrs is a dict of device pointers named as
+        the fields of the C struct (out: x, status; audit: metrics, flags; state: the four arrays; slots: count,
+        index, adopted and the ten arrays of `cap` slots)."""
+        b, o = packed.struct(dev_ptrs), repair_opts(pad=pad, max_raise=max_raise)
+        r, a = _struct_of(ObcaResult, out_ptrs), _struct_of(AuditResult, audit_ptrs)
+        s, sl = _struct_of(RepairState, state_ptrs), _struct_of(RepairSlots, slot_ptrs, cap=int(cap))
+        self._repair_call("htp_obca_repair_pack_batch_device", ctypes.byref(b), ctypes.byref(r), ctypes.byref(a),
+                          ctypes.byref(o), ctypes.byref(s), ctypes.byref(sl), stream)
+
+    def repair_merge_device(self, packed, dev_ptrs, slot_ptrs, cap, re_ptrs, re_audit_ptrs, out_ptrs, audit_ptrs,
+                            state_ptrs, tally_ptr=None, stream=None):
+        """Device-resident merge on `stream`, not synchronised (dicts as repair_pack_device)."""
+        b, sl = packed.struct(dev_ptrs), _struct_of(RepairSlots, slot_ptrs, cap=int(cap))
+        r1, a1 = _struct_of(ObcaResult, re_ptrs), _struct_of(AuditResult, re_audit_ptrs)
+        r0, a0, s = _struct_of(ObcaResult, out_ptrs), _struct_of(AuditResult, audit_ptrs), _struct_of(RepairState, state_ptrs)
+        self._repair_call("htp_obca_repair_merge_batch_device", ctypes.byref(b), ctypes.byref(sl), ctypes.byref(r1),
+                          ctypes.byref(a1), ctypes.byref(r0), ctypes.byref(a0), ctypes.byref(s), tally_ptr, stream)
+
+    def repair(self, packed, res, rounds=3, pad=0.01, max_raise=0.5, stage=True, **audit_opts_):
+        """The repair loop over host arrays: HostResults `res` of `packed` is updated in place with the re-solves
+        that were adopted -> (AuditResults of the adopted results, RepairReports).  Overwrites last_kernel_ms."""
+        aud, rep = AuditResults(packed.batch, packed.N, stage), RepairReports(packed.batch)
+        b, r, a, rp = packed.struct(), res.struct(), aud.struct(), rep.report_struct()
+        o = repair_opts(rounds, pad, max_raise, **audit_opts_)
+        self._repair_call("htp_obca_repair_batch", ctypes.byref(b), ctypes.byref(r), ctypes.byref(o), ctypes.byref(a),
+                          ctypes.byref(rp))
+        return aud, rep
+
+    def repair_device(self, packed, dev_ptrs, out_ptrs, audit_ptrs, state_ptrs, round_counts_ptr, rounds=3, pad=0.01,
+                      max_raise=0.5, stream=None, **audit_opts_):
+        """The repair loop over device arrays on `stream` (it synchronises the stream once per round to read the
+        count back; the last merge is left enqueued).  out_ptrs: the solve's seven result arrays, updated in place;
+        audit_ptrs: metrics, worst, flags (and stage_clearance), written; state_ptrs and round_counts_ptr [8, 3]:
+        the report, written."""
+        b, r, a = packed.struct(dev_ptrs), _struct_of(ObcaResult, out_ptrs), _struct_of(AuditResult, audit_ptrs)
+        rp = RepairReport()
+        rp.state, rp.round_counts = _struct_of(RepairState, state_ptrs), round_counts_ptr
+        o = repair_opts(rounds, pad, max_raise, **audit_opts_)
+        self._repair_call("htp_obca_repair_batch_device", ctypes.byref(b), ctypes.byref(r), ctypes.byref(o),
+                          ctypes.byref(a), ctypes.byref(rp), stream)
+
+    def repair_last_ms(self):
+        """(pack, merge) kernel times of the last pack and the last merge, ms."""
+        pk, mg = ctypes.c_double(), ctypes.c_double()
+        self.lib.htp_obca_repair_last_ms(self.ctx, ctypes.byref(pk), ctypes.byref(mg))
+        return pk.value, mg.value
 
     def resident_waves(self, packed):
         v = self.lib.htp_obca_resident_waves(self.ctx, ctypes.byref(packed.struct()))

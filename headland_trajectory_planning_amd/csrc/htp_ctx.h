@@ -18,6 +18,24 @@ struct htp_event_pair {
   }
 };
 
+// A device allocation grown on demand (ensure) and released with the context.
+struct htp_device_buffer {
+  void* p = nullptr;
+  size_t bytes = 0;
+  htp_device_buffer() = default;
+  htp_device_buffer(const htp_device_buffer&) = delete;
+  htp_device_buffer& operator=(const htp_device_buffer&) = delete;
+  ~htp_device_buffer() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+// Trajectory repair (htp_repair.hip): kernel timings, the selection (index, count) and the re-solve workspace.
+struct htp_repair_res {
+  htp_event_pair scan_ev, gather_ev, merge_ev;
+  htp_device_buffer sel, ws;
+};
+
 struct htp_ctx {
   using Options = htp::Options;
   using Shape = htp::Shape;
@@ -68,6 +86,8 @@ struct htp_ctx {
   htp_event_pair audit_ev;
   // trajectory timeline (htp_timeline.hip)
   htp_event_pair timeline_ev;
+  // trajectory repair (htp_repair.hip)
+  htp_repair_res repair;
 };
 
 static inline int fail(htp_ctx* c, const std::string& m) {

@@ -250,6 +250,21 @@ class OBCAOptimizer(object):
             x[-5 - (N - 1):-5] = solution["time_scale_opt"]
         return x
 
+    def _full_decision_vector(self, solution: Dict) -> np.ndarray:
+        """_decision_vector with the duals and the slack as well: what a warm-started re-solve starts from."""
+        N = self.N
+        x = self._decision_vector(solution)
+        o_mu = self.n_states * N + self.n_controls * (N - 1)
+        mu, la = np.asarray(solution["mu_opt"]).reshape(-1), np.asarray(solution["lambda_opt"]).reshape(-1)
+        x[o_mu:o_mu + mu.size] = mu
+        x[o_mu + mu.size:o_mu + mu.size + la.size] = la
+        x[-5:] = solution["slack_opt"]
+        return x
+
+    def repair(self, solution: Dict, **opts) -> Dict:
+        """One successful solution dict repaired where it loses the margin between nodes (see repair_batch)."""
+        return repair_batch([self], [solution], **opts)[0]
+
     def audit(self, solution: Dict, **opts) -> Dict:
         """Geometric audit of one solution dict (see audit_batch)."""
         return audit_batch([self], [solution], **opts)[0]
@@ -332,12 +347,50 @@ def timeline_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], dt: f
     return [res.as_dict(k) for k in range(pk.batch)]
 
 
+def _repair_entries(optimizers, pk, res, aud, rep, out):
+    for k, (o, (_, sol)) in enumerate(zip(optimizers, out)):
+        if int(rep.state[k]) & _native.REPAIR_STATES["IMPROVED"]:
+            sol.update(o._solution(res.x[k], res.objective[k]))
+        sol["audit"] = aud.as_dict(k)
+        sol["repair"] = rep.as_dict(k, pk.params[k, _native.P_DMIN])
+
+
+def repair_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], success: List[bool] = None,
+                 device: int = None, **opts) -> List[Dict]:
+    """Re-solve, on the device, the solutions that lose MIN_DISTANCE_TO_OBS between two nodes (no counterpart in the
+    reference, whose OBCA rows hold the margin at the N nodes only): every solution the audit flags COLLISION or
+    MARGIN is solved again with its margin raised by its own deficit plus `pad`, warm-started from its own
+    trajectory and duals, audited against the original margin, and kept where the dense clearance grew; up to
+    `rounds` times, never beyond `max_raise` above the original margin (_native.Context.repair; further keywords
+    are audit options).  success: one flag per solution (default: all succeeded); failed solves are left alone.
+    -> new solution dicts: the adopted trajectory with its "audit" entry and a "repair" entry (state names,
+    rounds, min_dist_used, extra_iterations)."""
+    if not optimizers:
+        return []
+    if len(optimizers) != len(solutions):
+        raise ValueError("[OBCA] repair_batch needs one solution per optimizer")
+    dev = optimizers[0].device if device is None else device
+    pk = _native.PackedBatch([o.instance() for o in optimizers])
+    res = _native.HostResults(pk.batch, pk.n_var)
+    res.x[:] = np.stack([o._full_decision_vector(s) for o, s in zip(optimizers, solutions)])
+    res.objective[:] = [s["objective"] for s in solutions]
+    if success is not None:   # any status outside {0, 1} keeps a problem out of the repair
+        res.status[:] = [0 if ok else 2 for ok in success]
+    aud, rep = _context(dev).repair(pk, res, **opts)
+    out = [(True, dict(s)) for s in solutions]
+    _repair_entries(optimizers, pk, res, aud, rep, out)
+    return [sol for _, sol in out]
+
+
 def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: int = None, max_cpu_time=None,
-                audit: Dict = None, timeline: Dict = None):
+                audit: Dict = None, timeline: Dict = None, repair: Dict = None):
     """Solve many OBCAOptimizer problems in one HIP launch -> [(success, solution)].
     max_cpu_time (seconds, per problem, device clock; None/<= 0: no limit).  audit: options of audit_batch
     (a dict, possibly empty); when given, every solution dict gets an "audit" entry.  timeline: dict(dt=...);
-    when given, every solution dict gets a "timeline" entry (see timeline_batch)."""
+    when given, every solution dict gets a "timeline" entry (see timeline_batch).  repair: options of repair_batch
+    (a dict, possibly empty); when given, the flagged successes are re-solved before anything else is derived:
+    the returned trajectory is the adopted one, and every solution dict gets a "repair" entry and the final
+    "audit" entry (made with the repair's audit options)."""
     if not optimizers:
         return []
     dev = optimizers[0].device if device is None else device
@@ -356,6 +409,10 @@ def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: 
             print(f"[OBCA] iterations {res.iterations[k]}, factorizations {res.n_factor[k]}, "
                   f"nlp error {res.nlp_error[k]:.3e}")
         out.append((bool(res.status[k] in (0, 1)), o._solution(res.x[k], res.objective[k])))
+    if repair is not None:
+        aud, rep = ctx.repair(pk, res, **{**(audit or {}), **repair})
+        _repair_entries(optimizers, pk, res, aud, rep, out)
+        audit = None   # the repair's audit (the audit options, overridden by the repair's) is the final one
     if audit is not None:
         aud = ctx.audit(pk, res.x, **audit)
         for k, (_, sol) in enumerate(out):

@@ -265,6 +265,103 @@ int htp_obca_timeline_batch_device(htp_ctx* ctx, const htp_obca_batch* in, const
 double htp_obca_timeline_last_ms(htp_ctx* ctx);
 
 /* ---------------------------------------------------------------------------
+ * Repair of solves that lose the margin between nodes (no reference counterpart: the OBCA rows of
+ * R/obca_py/optimizer.py:386-425 hold MIN_DISTANCE_TO_OBS at the N nodes and nowhere else, so a successful
+ * solve may still carry HTP_AUDIT_COLLISION or HTP_AUDIT_MARGIN).  A flagged problem is solved again with its
+ * margin raised by its own deficit, warm-started from its own X, U, mu and lambda, audited against the
+ * ORIGINAL margin, and its result is kept where the dense clearance grew.  Two steps, pack and merge, and the
+ * loop that runs them around htp_obca_solve_batch_device and htp_obca_audit_batch_device.
+ *   Per-problem state (htp_obca_repair_state): all-zero arrays are a fresh state.  A problem is RETIRED once it
+ *   carries RESOLVE_FAILED or GAVE_UP.  dmin_used is read only where rounds_used > 0.
+ *   Pack.  Problem p is a candidate when out->status[p] is 0 or 1, audit->flags[p] has COLLISION or MARGIN and
+ *   neither NONFINITE nor BAD_POLYTOPE, and p is not retired.  Its next margin is
+ *     dmin_cur + (dmin_orig - clearance) + pad          (doubles, left to right)
+ *   with dmin_orig = in->params[p][HTP_P_DMIN], dmin_cur = dmin_used[p] (dmin_orig before the first round) and
+ *   clearance = audit->metrics[p][HTP_AUDIT_CLEARANCE].  A candidate whose next margin is not
+ *   <= dmin_orig + max_raise is not packed: it gets CANDIDATE | GAVE_UP.  The others get CANDIDATE and are numbered
+ *   in ascending problem order: count = their number, index[s] = the problem of slot s, and slot s < cap receives
+ *   a complete htp_obca_batch row: traj (rows 1..N-2 = X_i of out->x, rows 0 and N-1 the rows of in->traj, bit for
+ *   bit: they are the NLP's start and end state), init_control = U, init_mu / init_lambda = the mu / lambda blocks
+ *   of out->x, the four polygon arrays, params_audit = in->params[p], params = the same with HTP_P_DMIN = the next
+ *   margin and both HTP_P_HAS_INIT_* slots 1.  With count > cap the first cap slots are written; slots at or beyond
+ *   min(count, cap) never are.  The solver has no input for tau: a re-solve starts at tau = 1, as the reference's
+ *   solver does.
+ *   Merge.  `re` / `re_audit`: the solve of the packed batch and its audit made with params_audit (slot-major).
+ *   Slot s < min(count, cap) is ADOPTED if and only if re->status[s] is 0 or 1, re_audit->flags[s] has neither
+ *   NONFINITE nor BAD_POLYTOPE and no bit outside COLLISION | MARGIN that audit->flags[p] lacks, and its
+ *   HTP_AUDIT_CLEARANCE is strictly larger than the adopted one.  An adopted slot replaces out->x[p] (the whole row),
+ *   every result field and every audit row of p = index[s]; adopted[s] = 1.  In every case dmin_used[p] = the
+ *   slot's margin, rounds_used[p] += 1, extra_iterations[p] += re->iterations[s], and state[p] gains IMPROVED
+ *   (adopted), REPAIRED (adopted and neither COLLISION nor MARGIN left), RESOLVE_FAILED (status outside {0, 1}:
+ *   p keeps its adopted result and is retired).  Problems that were never candidates are never written. */
+#define HTP_REPAIR_MAX_ROUNDS 8
+enum {                               /* int32 state[batch] */
+  HTP_REPAIR_CANDIDATE = 1,          /* was selected at least once */
+  HTP_REPAIR_IMPROVED = 2,           /* a re-solve was adopted */
+  HTP_REPAIR_REPAIRED = 4,           /* the adopted result is clean against the original margin */
+  HTP_REPAIR_RESOLVE_FAILED = 8,     /* a re-solve ended outside {0, 1}; retired */
+  HTP_REPAIR_GAVE_UP = 16            /* the next margin would exceed dmin_orig + max_raise; retired */
+};
+typedef struct {
+  int32_t rounds;                    /* 1..HTP_REPAIR_MAX_ROUNDS (pack and merge do not read it) */
+  double pad;                        /* >= 0, added to every raise */
+  double max_raise;                  /* > 0 */
+  htp_obca_audit_opts audit;         /* of every audit the loop makes (pack and merge do not read it) */
+} htp_obca_repair_opts;              /* defaults of the bindings: 3 rounds, pad 0.01 m, max_raise 0.5 m */
+typedef struct {
+  int32_t* state;                    /* [batch] HTP_REPAIR_* bits */
+  int32_t* rounds_used;              /* [batch] re-solves merged */
+  int32_t* extra_iterations;         /* [batch] their IPM iterations, adopted or not */
+  double* dmin_used;                 /* [batch] the margin of the last re-solve merged */
+} htp_obca_repair_state;
+typedef struct {
+  int32_t cap;                       /* slots of storage, >= 1 */
+  int32_t* count;                    /* [1] candidates packed (may exceed cap) */
+  int32_t* index;                    /* [cap] */
+  int32_t* adopted;                  /* [cap] written by merge */
+  double *traj, *obs_A, *obs_b, *body_G, *body_g, *params, *params_audit;   /* [cap][..] as in htp_obca_batch */
+  double *init_control, *init_mu, *init_lambda;
+} htp_obca_repair_slots;
+typedef struct {
+  htp_obca_repair_state state;
+  int32_t* round_counts;             /* [HTP_REPAIR_MAX_ROUNDS][3]: selected, adopted, clean; rounds not run: 0 */
+} htp_obca_repair_report;
+/* API errors (-1 with a "[repair]" message, nothing launched): a null required argument (out->n_resto,
+ * stage_clearance and tally may be null), N < 2 or > HTP_AUDIT_MAX_N, an edge count outside 3..8, cap < 1, pad
+ * not >= 0, max_raise not > 0, rounds outside 1..HTP_REPAIR_MAX_ROUNDS, audit options the audit rejects.
+ * batch == 0 returns 0.  The host variants are synchronous; the device variants are enqueued on `stream`. */
+int htp_obca_repair_pack_batch(htp_ctx* ctx, const htp_obca_batch* in, const htp_obca_result* out,
+                               const htp_obca_audit_result* audit, const htp_obca_repair_opts* opts,
+                               htp_obca_repair_state* state, htp_obca_repair_slots* slots);
+int htp_obca_repair_pack_batch_device(htp_ctx* ctx, const htp_obca_batch* in, const htp_obca_result* out,
+                                      const htp_obca_audit_result* audit, const htp_obca_repair_opts* opts,
+                                      htp_obca_repair_state* state, htp_obca_repair_slots* slots, void* stream);
+/* tally: nullable [3], incremented by the slots merged, adopted and clean */
+int htp_obca_repair_merge_batch(htp_ctx* ctx, const htp_obca_batch* in, const htp_obca_repair_slots* slots,
+                                const htp_obca_result* re, const htp_obca_audit_result* re_audit,
+                                htp_obca_result* out, htp_obca_audit_result* audit, htp_obca_repair_state* state,
+                                int32_t* tally);
+int htp_obca_repair_merge_batch_device(htp_ctx* ctx, const htp_obca_batch* in, const htp_obca_repair_slots* slots,
+                                       const htp_obca_result* re, const htp_obca_audit_result* re_audit,
+                                       htp_obca_result* out, htp_obca_audit_result* audit,
+                                       htp_obca_repair_state* state, int32_t* tally, void* stream);
+/* The loop: audits out->x into audit_out, then up to opts->rounds times: pack (into a workspace the library owns,
+ * sized by the count), htp_obca_solve_batch_device, htp_obca_audit_batch_device against params_audit, merge; it
+ * stops early when nothing is packed.  `out` is updated in place, audit_out ends as the audit of the adopted
+ * results, report->state starts fresh.  The device variant runs on `stream` and reads back 4 bytes (count) per
+ * round, because the solve entry takes its batch size on the host: it synchronises the stream once per round and
+ * returns with the last merge enqueued.  in->init_* are not read.  Overwrites htp_last_kernel_ms (the last
+ * re-solve) and htp_obca_audit_last_ms. */
+int htp_obca_repair_batch(htp_ctx* ctx, const htp_obca_batch* in, htp_obca_result* out,
+                          const htp_obca_repair_opts* opts, htp_obca_audit_result* audit_out,
+                          htp_obca_repair_report* report);
+int htp_obca_repair_batch_device(htp_ctx* ctx, const htp_obca_batch* in, htp_obca_result* out,
+                                 const htp_obca_repair_opts* opts, htp_obca_audit_result* audit_out,
+                                 htp_obca_repair_report* report, void* stream);
+/* durations (ms) of the last pack (scan + gather kernels) and the last merge (decide + scatter kernels) */
+int htp_obca_repair_last_ms(htp_ctx* ctx, double* pack_ms, double* merge_ms);
+
+/* ---------------------------------------------------------------------------
  * Warm start -> OBCA initial guess (R/obca_py/util.py get_init_ref_path :62-113
  * with cubic_spline.calc_spline_course :92-112): split at gear changes,
  * re-spline every segment over arc length at ds, v = gear * desired_v,
