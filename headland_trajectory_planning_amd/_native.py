@@ -163,6 +163,124 @@ class TimelineResults:
         return d
 
 
+class EnvelopeOpts(ctypes.Structure):  # htp_obca_envelope_opts
+    _fields_ = [("substeps", ctypes.c_int32), ("res", ctypes.c_double), ("W", ctypes.c_int32), ("H", ctypes.c_int32)]
+
+
+class EnvelopeResult(ctypes.Structure):  # htp_obca_envelope_result
+    _fields_ = [(n, ctypes.c_void_p) for n in ("extent", "where", "extent_body", "cells", "bitmap", "flags")]
+
+
+ENVELOPE_SIDES = ("umin", "umax", "vmin", "vmax")
+ENVELOPE_FLAGS = {"CLIPPED": 1, "NONFINITE": 2, "BAD_POLYTOPE": 4}
+ENVELOPE_MAX_N = 480
+ENVELOPE_MAX_CELLS = 65536
+
+
+def envelope_opts(substeps=4, res=0.1, W=0, H=0):
+    return EnvelopeOpts(int(substeps), float(res), int(W), int(H))
+
+
+def body_radius(packed):
+    """Largest distance of a body vertex from the body frame's origin, over the batch: the vertices are the pairwise
+    intersections of a body's rows that satisfy all of its rows."""
+    r = 0.0
+    off = np.concatenate([[0], np.cumsum(packed.body_edges)])
+    seen = set()
+    for p in range(packed.batch):
+        for k in range(packed.K):
+            G, g = packed.body_G[p, off[k]:off[k + 1]], packed.body_g[p, off[k]:off[k + 1]]
+            key = G.tobytes() + g.tobytes()
+            if key in seen:               # a fleet of one machine: the same rows in every problem
+                continue
+            seen.add(key)
+            for a in range(len(g)):
+                for b in range(a + 1, len(g)):
+                    A = np.array([G[a], G[b]])
+                    if abs(np.linalg.det(A)) < 1e-12:
+                        continue
+                    v = np.linalg.solve(A, np.array([g[a], g[b]]))
+                    if np.all(G @ v <= g + 1e-9 * (1.0 + np.abs(g))):
+                        r = max(r, float(np.hypot(v[0], v[1])))
+    return r
+
+
+def envelope_default_frame(packed, x, res):
+    """The frame Context.envelope uses when none is given -> (frames [batch, 3], W, H): phi = 0, origin = the
+    problem's own nodes' minimum minus pad, pad = the largest body-vertex radius + res, and the smallest admissible
+    W (a multiple of 32) and H that cover every problem's nodes' maximum plus pad.  Problems with a non-finite node
+    take no part in the sizes (the envelope rejects them)."""
+    if not (np.isfinite(res) and res > 0):
+        raise ValueError(f"[htp] envelope: res must be finite and > 0, got {res}")
+    B, N = packed.batch, packed.N
+    xy = np.asarray(x)[:, :5 * N].reshape(B, N, 5)[:, :, :2]
+    pad = body_radius(packed) + res
+    lo, hi = xy.min(axis=1) - pad, xy.max(axis=1) + pad
+    frames = np.zeros((B, 3))
+    good = np.all(np.isfinite(lo) & np.isfinite(hi), axis=1)
+    frames[good, :2] = lo[good]
+    span = (hi - lo)[good].max(axis=0) if good.any() else np.array([res, res])
+    W = max(32, 32 * int(np.ceil(np.ceil(span[0] / res) / 32.0)))
+    H = max(1, int(np.ceil(span[1] / res)))
+    if W * H > ENVELOPE_MAX_CELLS:
+        need = float(np.sqrt(span[0] * span[1] / ENVELOPE_MAX_CELLS))
+        raise ValueError(f"[htp] envelope: the default grid would be {W} x {H} cells at res = {res}, more than "
+                         f"{ENVELOPE_MAX_CELLS}; use a coarser res (about {1.1 * need:.3g} or more) or give frames, W and H")
+    return frames, W, H
+
+
+class EnvelopeResults:
+    """Host arrays of one envelope: extent [rows, 4] (ENVELOPE_SIDES), where [rows, 4, 3] (stage, substep, body),
+    extent_body [rows, K, 4], cells [rows, K + 1] (the union last), flags [rows] (ENVELOPE_FLAGS bits), words
+    [rows, H, W / 32] uint32 or None, and the frames, res, W and H they were computed in."""
+    SIDES = ENVELOPE_SIDES
+    FLAGS = ENVELOPE_FLAGS
+
+    def __init__(self, rows, K, W=0, H=0, res=0.0, frames=None, bitmap=True):
+        self.K, self.W, self.H, self.res = int(K), int(W), int(H), float(res)
+        self.frames = None if frames is None else np.ascontiguousarray(frames, dtype=np.float64)
+        self.extent = np.zeros((rows, 4))
+        self.where = np.zeros((rows, 4, 3), dtype=np.int32)
+        self.extent_body = np.zeros((rows, self.K, 4))
+        self.cells = np.zeros((rows, self.K + 1), dtype=np.int32)
+        self.flags = np.zeros(rows, dtype=np.int32)
+        self.words = np.zeros((rows, self.H, self.W // 32), dtype=np.uint32) if (bitmap and self.W > 0) else None
+
+    def struct(self):
+        r = EnvelopeResult()
+        r.extent, r.where, r.flags = self.extent.ctypes.data, self.where.ctypes.data, self.flags.ctypes.data
+        r.extent_body, r.cells = self.extent_body.ctypes.data, self.cells.ctypes.data
+        r.bitmap = None if self.words is None else self.words.ctypes.data
+        return r
+
+    def flag_names(self, k):
+        return [n for n, bit in ENVELOPE_FLAGS.items() if int(self.flags[k]) & bit]
+
+    def bitmap(self, k):
+        """The union's occupancy of problem k as bool [H, W]: element [j, i] is cell (i, j)."""
+        if self.words is None:
+            raise ValueError("[htp] envelope: no bitmap was asked for")
+        bits = (self.words[k][:, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]) & np.uint32(1)
+        return bits.reshape(self.H, self.W).astype(bool)
+
+    def as_dict(self, k):
+        d = {n: float(self.extent[k, j]) for j, n in enumerate(ENVELOPE_SIDES)}
+        d["depth"] = d["vmax"] - d["vmin"]
+        d["where"] = {n: dict(zip(("stage", "substep", "body"), (int(v) for v in self.where[k, j])))
+                      for j, n in enumerate(ENVELOPE_SIDES)}
+        d["extent_body"] = self.extent_body[k].copy()
+        d["flags"] = self.flag_names(k)
+        if self.frames is not None:
+            d["frame"] = self.frames[k].copy()
+        if self.W > 0:
+            d["cells"] = self.cells[k].copy()
+            d["area"] = float(self.cells[k, -1]) * self.res * self.res
+            d["res"], d["W"], d["H"] = self.res, self.W, self.H
+            if self.words is not None:
+                d["bitmap"] = self.bitmap(k)
+        return d
+
+
 class RepairOpts(ctypes.Structure):  # htp_obca_repair_opts
     _fields_ = [("rounds", ctypes.c_int32), ("pad", ctypes.c_double), ("max_raise", ctypes.c_double),
                 ("audit", AuditOpts)]
@@ -337,7 +455,8 @@ EXPORTS = ["htp_obca_sizes", "htp_create", "htp_destroy", "htp_last_error", "htp
            "htp_obca_timeline_batch", "htp_obca_timeline_batch_device", "htp_obca_timeline_last_ms",
            "htp_obca_repair_pack_batch", "htp_obca_repair_pack_batch_device", "htp_obca_repair_merge_batch",
            "htp_obca_repair_merge_batch_device", "htp_obca_repair_batch", "htp_obca_repair_batch_device",
-           "htp_obca_repair_last_ms"]
+           "htp_obca_repair_last_ms",
+           "htp_obca_envelope_batch", "htp_obca_envelope_batch_device", "htp_obca_envelope_last_ms"]
 
 
 def _declare(lib):
@@ -468,6 +587,15 @@ def _declare(lib):
             g.restype = ctypes.c_int
         lib.htp_obca_repair_last_ms.argtypes = [ctypes.c_void_p, _dp, _dp]
         lib.htp_obca_repair_last_ms.restype = ctypes.c_int
+    if hasattr(lib, "htp_obca_envelope_batch"):   # likewise
+        lib.htp_obca_envelope_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(ObcaBatch), ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.POINTER(EnvelopeOpts),
+                                                ctypes.POINTER(EnvelopeResult)]
+        lib.htp_obca_envelope_batch.restype = ctypes.c_int
+        lib.htp_obca_envelope_batch_device.argtypes = lib.htp_obca_envelope_batch.argtypes + [ctypes.c_void_p]
+        lib.htp_obca_envelope_batch_device.restype = ctypes.c_int
+        lib.htp_obca_envelope_last_ms.argtypes = [ctypes.c_void_p]
+        lib.htp_obca_envelope_last_ms.restype = ctypes.c_double
     if hasattr(lib, "htp_mfma_f64_probe"):   # absent from libraries built before it (A/B variants of old kernels)
         lib.htp_mfma_f64_probe.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
         lib.htp_mfma_f64_probe.restype = ctypes.c_int
@@ -1381,6 +1509,50 @@ class Context:
 
     def timeline_last_ms(self):
         return self.lib.htp_obca_timeline_last_ms(self.ctx)
+
+    def envelope(self, packed, x, frames=None, res=0.1, W=None, H=None, substeps=4, bitmap=True):
+        """Swept-footprint envelope of decision vectors x [batch, n_var] of `packed` (host buffers) ->
+        EnvelopeResults.  frames [batch, 3] = (ox, oy, phi) with the grid W x H of side res; frames=None takes the
+        default frame and grid (envelope_default_frame); W = H = 0 asks for the extent only."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (packed.batch, packed.n_var):
+            raise ValueError(f"[htp] envelope: x must be [{packed.batch}, {packed.n_var}], got {x.shape}")
+        if frames is None:
+            frames, W0, H0 = envelope_default_frame(packed, x, res)
+            W, H = (W0, H0) if W is None and H is None else (W, H)
+        frames = np.ascontiguousarray(frames, dtype=np.float64)
+        if frames.shape != (packed.batch, 3):
+            raise ValueError(f"[htp] envelope: frames must be [{packed.batch}, 3], got {frames.shape}")
+        if W is None or H is None:
+            raise ValueError("[htp] envelope: W and H must be given with frames (0, 0 for the extent only)")
+        ok = W > 0 and H > 0 and W % 32 == 0 and W * H <= ENVELOPE_MAX_CELLS   # otherwise the library refuses
+        res_ = EnvelopeResults(packed.batch, packed.K, W if ok else 0, H if ok else 0, res, frames, bitmap)
+        b, r = packed.struct(), res_.struct()
+        o = envelope_opts(substeps, res, W, H)
+        rc = self.lib.htp_obca_envelope_batch(self.ctx, ctypes.byref(b), x.ctypes.data, frames.ctypes.data,
+                                              ctypes.byref(o), ctypes.byref(r))
+        if rc != 0:
+            raise RuntimeError(f"[htp] htp_obca_envelope_batch failed: {self.error()}")
+        return res_
+
+    def envelope_device(self, packed, dev_ptrs, x_ptr, frame_ptr, out_ptrs, res=0.1, W=0, H=0, substeps=4,
+                        stream=None, lo=None, hi=None):
+        """Device-resident envelope of `packed` (or of its problems [lo, hi)) on `stream`, not synchronised.
+        x_ptr: device pointer of the [batch, n_var] rows (e.g. a solve's out x); frame_ptr: device [batch, 3];
+        out_ptrs: device pointers extent, where, flags and optionally extent_body, cells (required with a
+        raster) and bitmap (torch tensors' data_ptr())."""
+        b = packed.struct(dev_ptrs) if lo is None else packed.chunk_struct(dev_ptrs, lo, hi)
+        r = EnvelopeResult()
+        for k, v in out_ptrs.items():
+            setattr(r, k, v)
+        o = envelope_opts(substeps, res, W, H)
+        rc = self.lib.htp_obca_envelope_batch_device(self.ctx, ctypes.byref(b), x_ptr, frame_ptr, ctypes.byref(o),
+                                                     ctypes.byref(r), stream)
+        if rc != 0:
+            raise RuntimeError(f"[htp] htp_obca_envelope_batch_device failed: {self.error()}")
+
+    def envelope_last_ms(self):
+        return self.lib.htp_obca_envelope_last_ms(self.ctx)
 
     def _repair_call(self, name, *args):
         if getattr(self.lib, name)(self.ctx, *args) != 0:

@@ -88,6 +88,8 @@ struct htp_ctx {
   htp_event_pair timeline_ev;
   // trajectory repair (htp_repair.hip)
   htp_repair_res repair;
+  // trajectory envelope (htp_envelope.hip)
+  htp_event_pair envelope_ev;
 };
 
 static inline int fail(htp_ctx* c, const std::string& m) {

@@ -273,6 +273,10 @@ class OBCAOptimizer(object):
         """One solution dict sampled every dt seconds (see timeline_batch)."""
         return timeline_batch([self], [solution], dt)[0]
 
+    def envelope(self, solution: Dict, **opts) -> Dict:
+        """Swept-footprint envelope of one solution dict (see envelope_batch)."""
+        return envelope_batch([self], [solution], **opts)[0]
+
     # ------------------------------------------------------------- solve
     def solve(self, max_cpu_time=20, verbose: bool = False) -> Tuple[bool, Dict]:
         """optimizer.py:475-571.  max_cpu_time (IPOPT option, optimizer.py:486) limits
@@ -347,6 +351,25 @@ def timeline_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], dt: f
     return [res.as_dict(k) for k in range(pk.batch)]
 
 
+def envelope_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], device: int = None, **opts) -> List[Dict]:
+    """Measure, on the device, the ground that the trajectories of solution dicts sweep (the reference asks this of
+    warm starts only, car_model.py:39-73 get_path_poly): the extent (umin, umax, vmin, vmax) of the placed body
+    polygons over the nodes and `substeps` poses per interval in the frame (ox, oy, phi) of each problem, the
+    (stage, substep, body) that attains each side, and an occupancy raster of W x H cells of side `res` anchored at
+    the frame's origin: occupied cells per body and of the union, the area and the union as bool [H, W]
+    (_native.Context.envelope; options frames, res, W, H, substeps, bitmap; without frames the default frame
+    around each solution's own nodes) -> one dict per solution."""
+    if not optimizers:
+        return []
+    if len(optimizers) != len(solutions):
+        raise ValueError("[OBCA] envelope_batch needs one solution per optimizer")
+    dev = optimizers[0].device if device is None else device
+    pk = _native.PackedBatch([o.instance() for o in optimizers])
+    x = np.stack([o._decision_vector(s) for o, s in zip(optimizers, solutions)])
+    res = _context(dev).envelope(pk, x, **opts)
+    return [res.as_dict(k) for k in range(pk.batch)]
+
+
 def _repair_entries(optimizers, pk, res, aud, rep, out):
     for k, (o, (_, sol)) in enumerate(zip(optimizers, out)):
         if int(rep.state[k]) & _native.REPAIR_STATES["IMPROVED"]:
@@ -383,14 +406,15 @@ def repair_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], success
 
 
 def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: int = None, max_cpu_time=None,
-                audit: Dict = None, timeline: Dict = None, repair: Dict = None):
+                audit: Dict = None, timeline: Dict = None, repair: Dict = None, envelope: Dict = None):
     """Solve many OBCAOptimizer problems in one HIP launch -> [(success, solution)].
     max_cpu_time (seconds, per problem, device clock; None/<= 0: no limit).  audit: options of audit_batch
     (a dict, possibly empty); when given, every solution dict gets an "audit" entry.  timeline: dict(dt=...);
     when given, every solution dict gets a "timeline" entry (see timeline_batch).  repair: options of repair_batch
     (a dict, possibly empty); when given, the flagged successes are re-solved before anything else is derived:
     the returned trajectory is the adopted one, and every solution dict gets a "repair" entry and the final
-    "audit" entry (made with the repair's audit options)."""
+    "audit" entry (made with the repair's audit options).  envelope: options of envelope_batch (a dict, possibly
+    empty); when given, every solution dict gets an "envelope" entry."""
     if not optimizers:
         return []
     dev = optimizers[0].device if device is None else device
@@ -421,4 +445,8 @@ def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: 
         tml = ctx.timeline(pk, res.x, **timeline)
         for k, (_, sol) in enumerate(out):
             sol["timeline"] = tml.as_dict(k)
+    if envelope is not None:
+        env = ctx.envelope(pk, res.x, **envelope)
+        for k, (_, sol) in enumerate(out):
+            sol["envelope"] = env.as_dict(k)
     return out

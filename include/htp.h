@@ -362,6 +362,77 @@ int htp_obca_repair_batch_device(htp_ctx* ctx, const htp_obca_batch* in, htp_obc
 int htp_obca_repair_last_ms(htp_ctx* ctx, double* pack_ms, double* merge_ms);
 
 /* ---------------------------------------------------------------------------
+ * Swept-footprint envelope of solved OBCA trajectories (the reference asks this of warm starts only:
+ * R/car_model.py:39-73 get_path_poly unions the body and implement rectangles over a path, and
+ * orchard_environment_OBCA fixes the headland's width; nothing there measures the optimised trajectory).  For
+ * every problem of a batch: the extent of the placed body polygons over the densely sampled trajectory in a
+ * caller-given frame, which pose and body attain it, and an occupancy raster of the swept region.
+ *   Poses: exactly the audit's.  The N nodes and, with substeps = S, S - 1 poses inside every interval, from
+ *   step(X_i, U_i, wheelbase, h_i q / S, time_opt), q = 1..S-1, h_i = dT tau_i (dT without time_opt): the NLP's
+ *   own integrator (midpoint rule with time_opt, Euler otherwise).  The last node starts no interval.  sin, cos
+ *   and tan are the planner libm's; no product and sum are contracted.
+ *   Bodies: the K polygons of body_G / body_g, by the audit's construction: every row's line is clipped
+ *   against the other rows of its polygon; an edge record is the unit normal (nx, ny), the offset bb, the start
+ *   point and the length; a redundant row is dropped; the start points of the surviving edges are the polygon's
+ *   vertices (vx, vy).  A body that is empty or unbounded is a bad polytope.  Obstacles are not read.
+ *   Frame: frame[batch][3] = (ox, oy, phi), (c_phi, s_phi) = the libm's sincos(phi).  A world point w has the
+ *   frame coordinates u = c_phi (wx - ox) + s_phi (wy - oy), v = c_phi (wy - oy) - s_phi (wx - ox).  For a
+ *   headland, u runs along the boundary and v into the headland; the library attaches no further meaning.
+ *   Extent: extent[batch][4] = (umin, umax, vmin, vmax) over every vertex of every body at every pose
+ *   (x, y, c = cos theta, s = sin theta): the world vertex is (x + (c vx - s vy), y + (s vx + c vy)).
+ *   where[batch][4][3] = the (stage, substep, body) that attains each of the four; ties go to the lowest
+ *   flattened index (stage S + substep) K + body.  extent_body (nullable) [batch][K][4]: the same per body.
+ *   Raster: W x H cells of side res anchored at the frame's origin, W a multiple of 32, W H <= 65 536.  Cell
+ *   (i, j) has the centre a = (i + 0.5) res, b = (j + 0.5) res, in the world
+ *   w = (ox + (c_phi a - s_phi b), oy + (s_phi a + c_phi b)), and in the body frame of a pose
+ *   q = (c dx + s dy, c dy - s dx) with (dx, dy) = w - (x, y).  Body k at a pose covers the cell iff
+ *   nx qx + ny qy - bb <= 0 for every surviving edge record of k.  A cell is occupied by body k iff some pose
+ *   covers it, and occupied iff some body occupies it.
+ *   cells[batch][K + 1]: occupied cells per body and, at index K, of the union.  bitmap (nullable) uint32
+ *   [batch][H][W / 32]: the union; bit b of word w in row j is cell (32 w + b, j).  Area = cells res^2 is the
+ *   caller's arithmetic.  W = H = 0 asks for the extent only: no raster work, cells and bitmap are not written,
+ *   res is not read.
+ *   `in` is the struct the solve took; only X, U and tau of x, the body rows, the frame and the dT and
+ *   wheelbase parameters are read, so a failed solve still gets an answer.  One wavefront per problem, one
+ *   launch.  The device equals a serial evaluation bit for bit: every quantity is a min / max with an index,
+ *   a bit OR or a population count. */
+#define HTP_ENVELOPE_MAX_N HTP_AUDIT_MAX_N   /* the LDS staging holds the audit's horizon beside a full grid */
+#define HTP_ENVELOPE_MAX_CELLS 65536
+enum {                               /* int32 flags[batch] */
+  HTP_ENVELOPE_CLIPPED = 1,          /* umin < 0, vmin < 0, umax > W res or vmax > H res: the counts and the bitmap
+                                        are of the part inside the grid (never set without a raster) */
+  HTP_ENVELOPE_NONFINITE = 2,        /* a non-finite double among those read, the frame included: extent NaN, where -1,
+                                        cells 0, bitmap zeroed, no other flag */
+  HTP_ENVELOPE_BAD_POLYTOPE = 4      /* a body that is empty or unbounded: the same outputs */
+};
+typedef struct {
+  int32_t substeps;                  /* 1 (nodes only) .. HTP_AUDIT_MAX_SUBSTEPS */
+  double res;                        /* cell side, finite and > 0 (not read when W = H = 0) */
+  int32_t W, H;                      /* cells along u and v; both 0: extent only */
+} htp_obca_envelope_opts;
+typedef struct {
+  double* extent;           /* [batch][4] umin, umax, vmin, vmax */
+  int32_t* where;           /* [batch][4][3] stage, substep, body of each */
+  double* extent_body;      /* nullable [batch][K][4] */
+  int32_t* cells;           /* [batch][K + 1]; may be null when W = H = 0 */
+  uint32_t* bitmap;         /* nullable [batch][H][W / 32] */
+  int32_t* flags;           /* [batch] HTP_ENVELOPE_* bits */
+} htp_obca_envelope_result;
+/* API errors (-1 with an "[envelope]" message, nothing launched): a null required argument, N < 2 or
+ * > HTP_ENVELOPE_MAX_N, substeps outside 1..HTP_AUDIT_MAX_SUBSTEPS, an edge count outside 3..8, res not finite
+ * or <= 0 when a raster is asked for, W not a multiple of 32, W H > HTP_ENVELOPE_MAX_CELLS, exactly one of W, H
+ * being 0.  batch == 0 returns 0. */
+/* host pointers, synchronous; only [X | U | tau] of every x row is uploaded */
+int htp_obca_envelope_batch(htp_ctx* ctx, const htp_obca_batch* in, const double* x, const double* frame,
+                            const htp_obca_envelope_opts* opts, htp_obca_envelope_result* out);
+/* device pointers, enqueued on `stream`, not synchronised: behind htp_obca_solve_batch_device (and the audit) on
+ * the same stream it measures that solve's out->x without a host round trip */
+int htp_obca_envelope_batch_device(htp_ctx* ctx, const htp_obca_batch* in, const double* x, const double* frame,
+                                   const htp_obca_envelope_opts* opts, htp_obca_envelope_result* out, void* stream);
+/* duration (ms) of the last envelope kernel (hipEvents on its stream) */
+double htp_obca_envelope_last_ms(htp_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * Warm start -> OBCA initial guess (R/obca_py/util.py get_init_ref_path :62-113
  * with cubic_spline.calc_spline_course :92-112): split at gear changes,
  * re-spline every segment over arc length at ds, v = gear * desired_v,
