@@ -281,6 +281,114 @@ class EnvelopeResults:
         return d
 
 
+class TrackOpts(ctypes.Structure):  # htp_obca_track_opts
+    _fields_ = [("dt", ctypes.c_double), ("max_ticks", ctypes.c_int32), ("plant_substeps", ctypes.c_int32),
+                ("k_lat", ctypes.c_double), ("k_yaw", ctypes.c_double), ("k_lon", ctypes.c_double),
+                ("abort_dist", ctypes.c_double), ("margin_tol", ctypes.c_double), ("R", ctypes.c_int32),
+                ("scenarios", ctypes.c_void_p)]
+
+
+class TrackResult(ctypes.Structure):  # htp_obca_track_result
+    _fields_ = [(n, ctypes.c_void_p) for n in ("metrics", "worst", "flags", "tally", "worst_scenario",
+                                               "tick_clearance", "reference")]
+
+
+TRACK_METRICS = ("clearance", "max_e_lat", "max_e_lon", "max_e_theta", "end_pos", "end_e_theta", "max_steer_dev",
+                 "sat_share")
+TRACK_FLAGS = {"COLLISION": 1, "MARGIN": 2, "SAT_STEER": 4, "SAT_RATE": 8, "SAT_ACC": 16, "DIVERGED": 32,
+               "TRUNCATED": 64, "NONFINITE": 128, "BAD_POLYTOPE": 256, "BAD_TIME": 512}
+TRACK_SCENARIO_COLUMNS = ("lat0", "lon0", "yaw0", "steer_bias", "slip", "yaw_gain")
+TRACK_REFERENCE_COLUMNS = ("x", "y", "v", "theta", "steer")
+TRACK_MAX_N = 480
+TRACK_MAX_SCENARIOS = 4096
+# Default gains, from the linearised error dynamics in include/htp.h: natural frequency |v| sqrt(k_lat / L), damping
+# ratio k_yaw / (2 sqrt(k_lat L)).  k_lat = 0.5 /m and k_yaw = 2 give, at the wheelbases 1.9-3 m of the machines
+# here, a damping ratio of 1.03-0.82, and at speeds of 1-2 m/s a natural frequency of 0.5-1 rad/s: at most a tenth of
+# a radian per 0.1 s control tick, far inside what the one-tick hold of the steering set-point tolerates.  k_lon = 1 /s closes
+# the along-track error with a 1 s time constant (k_lon dt = 0.1).
+TRACK_DEFAULT_GAINS = dict(k_lat=0.5, k_yaw=2.0, k_lon=1.0)
+
+
+def track_scenarios(R, seed, lat=0.05, lon=0.05, yaw=0.02, steer_bias=0.01, slip=0.03, yaw_gain=0.05):
+    """A seeded table [R, 6] (TRACK_SCENARIO_COLUMNS) of normal draws with the given standard deviations through
+    numpy.random.default_rng(seed): row 0 is the nominal scenario (0, 0, 0, 0, 0, 1); slip is clipped to [0, 0.5),
+    yaw_gain is drawn around 1."""
+    R = int(R)
+    if R < 1:
+        raise ValueError(f"[htp] track_scenarios: R must be >= 1, got {R}")
+    rng = np.random.default_rng(seed)
+    t = rng.normal(0.0, 1.0, (R, len(TRACK_SCENARIO_COLUMNS))) * np.array([lat, lon, yaw, steer_bias, slip, yaw_gain])
+    t[:, 4] = np.clip(t[:, 4], 0.0, np.nextafter(0.5, 0.0))
+    t[:, 5] += 1.0
+    t[0] = [0.0, 0.0, 0.0, 0.0, 0.0, 1.0]
+    return t
+
+
+def track_opts(dt, max_ticks, scenarios_ptr, R, plant_substeps=2, k_lat=TRACK_DEFAULT_GAINS["k_lat"],
+               k_yaw=TRACK_DEFAULT_GAINS["k_yaw"], k_lon=TRACK_DEFAULT_GAINS["k_lon"], abort_dist=2.0,
+               margin_tol=1e-4):
+    """htp_obca_track_opts.  scenarios_ptr: the address of R rows of 6 doubles (host or device, as the entry that
+    takes it); the caller keeps the array alive.  abort_dist 2 m: a machine that far off its path has left the
+    turn.  margin_tol as the audit's."""
+    return TrackOpts(float(dt), int(max_ticks), int(plant_substeps), float(k_lat), float(k_yaw), float(k_lon),
+                     float(abort_dist), float(margin_tol), int(R), scenarios_ptr)
+
+
+def track_ticks(packed, x, dt):
+    """Poses of storage that hold every problem of x [batch, n_var] at period dt (timeline_cap's count)."""
+    return timeline_cap(packed, x, dt)
+
+
+class TrackResults:
+    """Host arrays of one tracking rollout: metrics [rows, R, 8] (TRACK_METRICS), worst [rows, R, 3] (tick, obstacle,
+    body), flags [rows, R] (TRACK_FLAGS bits), tally [rows, 10] (scenarios per flag, in TRACK_FLAGS order),
+    worst_scenario [rows], tick_clearance [rows, max_ticks] or None, reference [rows, max_ticks, 5] or None (both
+    pre-filled with NaN: the poses a problem does not reach are never written), and the scenarios they belong to."""
+    METRICS = TRACK_METRICS
+    FLAGS = TRACK_FLAGS
+
+    def __init__(self, rows, R, max_ticks, scenarios=None, ticks=True, reference=False):
+        self.R, self.max_ticks = int(R), int(max_ticks)
+        self.scenarios = scenarios
+        self.metrics = np.zeros((rows, self.R, len(TRACK_METRICS)))
+        self.worst = np.zeros((rows, self.R, 3), dtype=np.int32)
+        self.flags = np.zeros((rows, self.R), dtype=np.int32)
+        self.tally = np.zeros((rows, len(TRACK_FLAGS)), dtype=np.int32)
+        self.worst_scenario = np.zeros(rows, dtype=np.int32)
+        self.tick_clearance = np.full((rows, self.max_ticks), np.nan) if ticks else None
+        self.reference = np.full((rows, self.max_ticks, len(TRACK_REFERENCE_COLUMNS)), np.nan) if reference else None
+
+    def struct(self):
+        r = TrackResult()
+        for n in ("metrics", "worst", "flags", "tally", "worst_scenario"):
+            setattr(r, n, getattr(self, n).ctypes.data)
+        r.tick_clearance = None if self.tick_clearance is None else self.tick_clearance.ctypes.data
+        r.reference = None if self.reference is None else self.reference.ctypes.data
+        return r
+
+    def metric(self, name):
+        return self.metrics[:, :, TRACK_METRICS.index(name)]
+
+    def flag_names(self, k, s):
+        return [n for n, bit in TRACK_FLAGS.items() if int(self.flags[k, s]) & bit]
+
+    def as_dict(self, k):
+        d = {n: self.metrics[k, :, j].copy() for j, n in enumerate(TRACK_METRICS)}
+        d["worst"] = self.worst[k].copy()
+        d["flags"] = [self.flag_names(k, s) for s in range(self.R)]
+        d["tally"] = {n: int(self.tally[k, j]) for j, n in enumerate(TRACK_FLAGS)}
+        d["worst_scenario"] = int(self.worst_scenario[k])
+        d["ok"] = not (int(np.bitwise_or.reduce(self.flags[k])) &
+                       ~(TRACK_FLAGS["SAT_STEER"] | TRACK_FLAGS["SAT_RATE"] | TRACK_FLAGS["SAT_ACC"]))
+        if self.scenarios is not None:
+            d["scenarios"] = self.scenarios.copy()
+        if self.tick_clearance is not None:
+            d["tick_clearance"] = self.tick_clearance[k].copy()
+        if self.reference is not None:
+            d["reference"] = self.reference[k].copy()
+        return d
+
+
 class RepairOpts(ctypes.Structure):  # htp_obca_repair_opts
     _fields_ = [("rounds", ctypes.c_int32), ("pad", ctypes.c_double), ("max_raise", ctypes.c_double),
                 ("audit", AuditOpts)]
@@ -456,7 +564,8 @@ EXPORTS = ["htp_obca_sizes", "htp_create", "htp_destroy", "htp_last_error", "htp
            "htp_obca_repair_pack_batch", "htp_obca_repair_pack_batch_device", "htp_obca_repair_merge_batch",
            "htp_obca_repair_merge_batch_device", "htp_obca_repair_batch", "htp_obca_repair_batch_device",
            "htp_obca_repair_last_ms",
-           "htp_obca_envelope_batch", "htp_obca_envelope_batch_device", "htp_obca_envelope_last_ms"]
+           "htp_obca_envelope_batch", "htp_obca_envelope_batch_device", "htp_obca_envelope_last_ms",
+           "htp_obca_track_batch", "htp_obca_track_batch_device", "htp_obca_track_last_ms"]
 
 
 def _declare(lib):
@@ -596,6 +705,14 @@ def _declare(lib):
         lib.htp_obca_envelope_batch_device.restype = ctypes.c_int
         lib.htp_obca_envelope_last_ms.argtypes = [ctypes.c_void_p]
         lib.htp_obca_envelope_last_ms.restype = ctypes.c_double
+    if hasattr(lib, "htp_obca_track_batch"):   # likewise
+        lib.htp_obca_track_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(ObcaBatch), ctypes.c_void_p,
+                                             ctypes.POINTER(TrackOpts), ctypes.POINTER(TrackResult)]
+        lib.htp_obca_track_batch.restype = ctypes.c_int
+        lib.htp_obca_track_batch_device.argtypes = lib.htp_obca_track_batch.argtypes + [ctypes.c_void_p]
+        lib.htp_obca_track_batch_device.restype = ctypes.c_int
+        lib.htp_obca_track_last_ms.argtypes = [ctypes.c_void_p]
+        lib.htp_obca_track_last_ms.restype = ctypes.c_double
     if hasattr(lib, "htp_mfma_f64_probe"):   # absent from libraries built before it (A/B variants of old kernels)
         lib.htp_mfma_f64_probe.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
         lib.htp_mfma_f64_probe.restype = ctypes.c_int
@@ -1553,6 +1670,52 @@ class Context:
 
     def envelope_last_ms(self):
         return self.lib.htp_obca_envelope_last_ms(self.ctx)
+
+    def track(self, packed, x, scenarios=None, dt=0.1, max_ticks=None, ticks=True, reference=False, R=64, seed=0,
+              **opts):
+        """Closed-loop tracking rollout of decision vectors x [batch, n_var] of `packed` under every scenario (host
+        buffers) -> TrackResults.  scenarios [R, 6] (TRACK_SCENARIO_COLUMNS); None draws track_scenarios(R, seed).
+        max_ticks: poses of storage per problem; None derives it from x (track_ticks), so that no problem is
+        truncated.  Further keywords: plant_substeps, k_lat, k_yaw, k_lon, abort_dist, margin_tol (track_opts)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (packed.batch, packed.n_var):
+            raise ValueError(f"[htp] track: x must be [{packed.batch}, {packed.n_var}], got {x.shape}")
+        if scenarios is None:
+            scenarios = track_scenarios(R, seed)
+        scenarios = np.ascontiguousarray(scenarios, dtype=np.float64)
+        if scenarios.ndim != 2 or scenarios.shape[1] != len(TRACK_SCENARIO_COLUMNS):
+            raise ValueError(f"[htp] track: scenarios must be [R, 6], got {scenarios.shape}")
+        if max_ticks is None:
+            if not (np.isfinite(dt) and dt > 0):
+                raise ValueError(f"[htp] track: dt must be finite and > 0, got {dt}")
+            max_ticks = track_ticks(packed, x, dt)
+        res = TrackResults(packed.batch, scenarios.shape[0], max(int(max_ticks), 0), scenarios, ticks, reference)
+        b, r = packed.struct(), res.struct()
+        o = track_opts(dt, max_ticks, scenarios.ctypes.data, scenarios.shape[0], **opts)
+        rc = self.lib.htp_obca_track_batch(self.ctx, ctypes.byref(b), x.ctypes.data, ctypes.byref(o), ctypes.byref(r))
+        if rc != 0:
+            raise RuntimeError(f"[htp] htp_obca_track_batch failed: {self.error()}")
+        return res
+
+    def track_device(self, packed, dev_ptrs, x_ptr, scenarios_ptr, R, out_ptrs, dt, max_ticks, stream=None, lo=None,
+                     hi=None, **opts):
+        """Device-resident tracking rollout of `packed` (or of its problems [lo, hi)) on `stream`, not synchronised.
+        x_ptr: device pointer of the [batch, n_var] rows (e.g. a solve's out x); scenarios_ptr: device [R, 6];
+        out_ptrs: device pointers metrics [batch, R, 8], worst [batch, R, 3], flags [batch, R], tally [batch, 10],
+        worst_scenario [batch] and optionally tick_clearance [batch, max_ticks] and reference [batch, max_ticks, 5]
+        (torch tensors' data_ptr())."""
+        b = packed.struct(dev_ptrs) if lo is None else packed.chunk_struct(dev_ptrs, lo, hi)
+        r = TrackResult()
+        for k, v in out_ptrs.items():
+            setattr(r, k, v)
+        o = track_opts(dt, max_ticks, scenarios_ptr, R, **opts)
+        rc = self.lib.htp_obca_track_batch_device(self.ctx, ctypes.byref(b), x_ptr, ctypes.byref(o), ctypes.byref(r),
+                                                  stream)
+        if rc != 0:
+            raise RuntimeError(f"[htp] htp_obca_track_batch_device failed: {self.error()}")
+
+    def track_last_ms(self):
+        return self.lib.htp_obca_track_last_ms(self.ctx)
 
     def _repair_call(self, name, *args):
         if getattr(self.lib, name)(self.ctx, *args) != 0:

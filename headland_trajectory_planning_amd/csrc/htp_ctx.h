@@ -90,6 +90,8 @@ struct htp_ctx {
   htp_repair_res repair;
   // trajectory envelope (htp_envelope.hip)
   htp_event_pair envelope_ev;
+  // tracking rollout (htp_track.hip)
+  htp_event_pair track_ev;
 };
 
 static inline int fail(htp_ctx* c, const std::string& m) {

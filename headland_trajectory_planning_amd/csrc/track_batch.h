@@ -1,0 +1,61 @@
+// htp_obca_batch + htp_obca_track_opts/result -> the track core's launch shape and pointer view, with the
+// argument checks of the C ABI; shared by the gfx950 library (htp_track.hip) and the test-only host build
+// (track_hostsim.cpp).
+#pragma once
+#include "../../include/htp.h"
+#include "track_core.h"
+
+namespace htp {
+namespace track {
+
+static_assert(HTP_TRACK_NMETRIC == 8 && HTP_TRACK_NDIST == 6 && HTP_TRACK_NFLAG == 10, "htp.h track sizes");
+
+// 0 = OK; -1 with *err set: nothing may be launched
+inline int check_args(const htp_obca_batch* in, const double* x, const htp_obca_track_opts* o,
+                      const htp_obca_track_result* out, const char** err) {
+  using audit::nonfinite_;
+  if (!in || !o || !out) { *err = "[track] null argument"; return -1; }
+  if (in->batch < 0) { *err = "[track] batch must be >= 0"; return -1; }
+  if (in->N < 2) { *err = "[track] N must be >= 2"; return -1; }
+  if (in->N > MAXN) { *err = "[track] N must be <= HTP_TRACK_MAX_N (480)"; return -1; }
+  if (in->M < 1 || in->M > MAXM) { *err = "[track] M must be in [1, 16]"; return -1; }
+  if (in->K < 1 || in->K > MAXK) { *err = "[track] K must be in [1, 4]"; return -1; }
+  if (nonfinite_(o->dt) || !(o->dt > 0.0)) { *err = "[track] dt must be finite and > 0"; return -1; }
+  if (o->max_ticks < 2) { *err = "[track] max_ticks must be >= 2"; return -1; }
+  if (o->plant_substeps < 1 || o->plant_substeps > HTP_TRACK_MAX_SUBSTEPS) {
+    *err = "[track] plant_substeps must be in [1, HTP_TRACK_MAX_SUBSTEPS (16)]";
+    return -1;
+  }
+  if (o->R < 1 || o->R > HTP_TRACK_MAX_SCENARIOS) { *err = "[track] R must be in [1, HTP_TRACK_MAX_SCENARIOS (4096)]"; return -1; }
+  if (nonfinite_(o->k_lat) || nonfinite_(o->k_yaw) || nonfinite_(o->k_lon) || !(o->k_lat >= 0.0) ||
+      !(o->k_yaw >= 0.0) || !(o->k_lon >= 0.0)) {
+    *err = "[track] gains k_lat, k_yaw and k_lon must be finite and >= 0";
+    return -1;
+  }
+  if (nonfinite_(o->margin_tol) || !(o->margin_tol >= 0.0)) { *err = "[track] margin_tol must be finite and >= 0"; return -1; }
+  if (!(o->abort_dist > 0.0)) { *err = "[track] abort_dist must be > 0"; return -1; }
+  if (!in->obs_edges || !in->body_edges) { *err = "[track] null argument (edge counts)"; return -1; }
+  for (int m = 0; m < in->M; ++m)
+    if (in->obs_edges[m] < 3 || in->obs_edges[m] > MAXE) { *err = "[track] obstacle edges must be in [3, 8]"; return -1; }
+  for (int k = 0; k < in->K; ++k)
+    if (in->body_edges[k] < 3 || in->body_edges[k] > MAXE) { *err = "[track] body edges must be in [3, 8]"; return -1; }
+  if (in->batch == 0) return 0;
+  if (!x || !in->obs_A || !in->obs_b || !in->body_G || !in->body_g || !in->params || !o->scenarios) {
+    *err = "[track] null argument (input array)";
+    return -1;
+  }
+  if (!out->metrics || !out->worst || !out->flags || !out->tally || !out->worst_scenario) {
+    *err = "[track] null argument (output array)";
+    return -1;
+  }
+  return 0;
+}
+
+inline Batch batch_view(const htp_obca_batch& in, const double* x, const htp_obca_track_opts& o,
+                        const htp_obca_track_result& out) {
+  return Batch{in.obs_A, in.obs_b, in.body_G, in.body_g, in.params, x, o.scenarios,
+               out.metrics, out.worst, out.flags, out.tally, out.worst_scenario, out.tick_clearance, out.reference};
+}
+
+}  // namespace track
+}  // namespace htp

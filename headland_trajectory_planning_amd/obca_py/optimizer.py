@@ -277,6 +277,10 @@ class OBCAOptimizer(object):
         """Swept-footprint envelope of one solution dict (see envelope_batch)."""
         return envelope_batch([self], [solution], **opts)[0]
 
+    def track(self, solution: Dict, **opts) -> Dict:
+        """Closed-loop tracking rollout of one solution dict (see track_batch)."""
+        return track_batch([self], [solution], **opts)[0]
+
     # ------------------------------------------------------------- solve
     def solve(self, max_cpu_time=20, verbose: bool = False) -> Tuple[bool, Dict]:
         """optimizer.py:475-571.  max_cpu_time (IPOPT option, optimizer.py:486) limits
@@ -370,6 +374,26 @@ def envelope_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], devic
     return [res.as_dict(k) for k in range(pk.batch)]
 
 
+def track_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], device: int = None, **opts) -> List[Dict]:
+    """Drive, on the device, a kinematic plant along the trajectories of solution dicts under a tracking controller
+    and a table of disturbance scenarios shared by all of them (no counterpart in the reference, which plans a turn
+    and stops there): initial lateral / longitudinal / heading offset, steering bias, slip and yaw gain per scenario;
+    the NLP's own steering, steering-rate, acceleration and speed limits; the clearance of the bodies against the
+    obstacles at every control tick (_native.Context.track; options scenarios or R and seed, dt, max_ticks,
+    plant_substeps, k_lat, k_yaw, k_lon, abort_dist, margin_tol, ticks, reference) -> one dict per solution: the
+    per-scenario arrays named in _native.TRACK_METRICS, worst (tick, obstacle, body), the flag names per scenario,
+    the tally of scenarios per flag and the worst scenario."""
+    if not optimizers:
+        return []
+    if len(optimizers) != len(solutions):
+        raise ValueError("[OBCA] track_batch needs one solution per optimizer")
+    dev = optimizers[0].device if device is None else device
+    pk = _native.PackedBatch([o.instance() for o in optimizers])
+    x = np.stack([o._decision_vector(s) for o, s in zip(optimizers, solutions)])
+    res = _context(dev).track(pk, x, **opts)
+    return [res.as_dict(k) for k in range(pk.batch)]
+
+
 def _repair_entries(optimizers, pk, res, aud, rep, out):
     for k, (o, (_, sol)) in enumerate(zip(optimizers, out)):
         if int(rep.state[k]) & _native.REPAIR_STATES["IMPROVED"]:
@@ -406,7 +430,8 @@ def repair_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], success
 
 
 def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: int = None, max_cpu_time=None,
-                audit: Dict = None, timeline: Dict = None, repair: Dict = None, envelope: Dict = None):
+                audit: Dict = None, timeline: Dict = None, repair: Dict = None, envelope: Dict = None,
+                track: Dict = None):
     """Solve many OBCAOptimizer problems in one HIP launch -> [(success, solution)].
     max_cpu_time (seconds, per problem, device clock; None/<= 0: no limit).  audit: options of audit_batch
     (a dict, possibly empty); when given, every solution dict gets an "audit" entry.  timeline: dict(dt=...);
@@ -414,7 +439,8 @@ def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: 
     (a dict, possibly empty); when given, the flagged successes are re-solved before anything else is derived:
     the returned trajectory is the adopted one, and every solution dict gets a "repair" entry and the final
     "audit" entry (made with the repair's audit options).  envelope: options of envelope_batch (a dict, possibly
-    empty); when given, every solution dict gets an "envelope" entry."""
+    empty); when given, every solution dict gets an "envelope" entry.  track: options of track_batch (a dict, possibly
+    empty); when given, every solution dict gets a "track" entry, of the repaired trajectory where a repair ran."""
     if not optimizers:
         return []
     dev = optimizers[0].device if device is None else device
@@ -449,4 +475,8 @@ def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: 
         env = ctx.envelope(pk, res.x, **envelope)
         for k, (_, sol) in enumerate(out):
             sol["envelope"] = env.as_dict(k)
+    if track is not None:
+        trk = ctx.track(pk, res.x, **track)
+        for k, (_, sol) in enumerate(out):
+            sol["track"] = trk.as_dict(k)
     return out

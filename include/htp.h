@@ -433,6 +433,125 @@ int htp_obca_envelope_batch_device(htp_ctx* ctx, const htp_obca_batch* in, const
 double htp_obca_envelope_last_ms(htp_ctx* ctx);
 
 /* ---------------------------------------------------------------------------
+ * Closed-loop tracking rollout of solved OBCA trajectories (no reference counterpart: the reference plans a turn
+ * and stops there).  For every problem of a batch and every one of R disturbance scenarios shared by the batch, a
+ * kinematic plant is driven along the solved trajectory by a fixed tracking controller with the NLP's own actuator
+ * limits, and the clearance of the placed bodies against the obstacles is measured at every control tick.
+ *   Read: X, U and tau of x; the four polygon arrays; params DT, WHEELBASE (L), MAXSTEER, MAXV, MAXACC, MAXSR (their
+ *   absolute values are the limits) and DMIN; the scenario table.  sin, cos, tan, atan2 and hypot are the planner
+ *   libm's; no product and sum are contracted.  clamp(u, +-m) = u < -m ? -m : (u > m ? m : u); it BITES when it
+ *   changes u.
+ *   Reference signal.  Node times t_i and T exactly as the timeline's (serial sums of h_i = dT tau_i, dT without
+ *   time_opt).  n = the smallest n with fl(n dt) >= T.  ref(k) for k < n is the timeline's regular row at
+ *   s_k = fl(k dt): step(X_i, U_i, L, s_k - t_i, time_opt) with i the largest i in 0..N-2 with t_i <= s_k; ref(k)
+ *   for k >= n is the stored node X_{N-1}.  Its five doubles are (xr, yr, vr, thr, dr).  Poses k = 0..n are
+ *   rolled; with n + 1 > max_ticks only the first max_ticks, and every scenario gets TRUNCATED.  np = the number
+ *   of poses rolled.
+ *   Problem-level rejections, as the timeline's: a non-finite double among those read from x, the polygons and
+ *   params -> NONFINITE; some h_i not > 0 or T / dt >= 2^30 -> BAD_TIME.  Then every scenario of the problem gets
+ *   metrics NaN, worst -1 and flags = that one bit; tally counts R under that bit; worst_scenario = -1;
+ *   tick_clearance and reference are not written.
+ *   Scenario row (lat0, lon0, yaw0, steer_bias, slip, yaw_gain).  A row with a non-finite double: metrics NaN,
+ *   worst -1, flags = NONFINITE alone; it takes no part in anything else.  Initial state, with (c0, s0) =
+ *   sincos(X_0.theta):  x = (X_0.x + lon0 c0) - lat0 s0,  y = (X_0.y + lon0 s0) + lat0 c0,  v = X_0.v,
+ *   theta = X_0.theta + yaw0,  delta = X_0.steer.
+ *   At pose k, with (c, s) = sincos(thr) of ref(k):
+ *     e_lon = c (x - xr) + s (y - yr),  e_lat = c (y - yr) - s (x - xr),  d = theta - thr,
+ *     e_th = atan2(sin d, cos d);
+ *     clearance_k = min over obstacles m and bodies b of the audit's signed_distance at (x, y, cos theta, sin theta),
+ *     over the audit's edge records; the running minimum keeps (k, m, b), ties to the lowest (k M + m) K + b.  An
+ *     empty or unbounded polygon (BAD_POLYTOPE, the audit's rule) makes the clearance metric NaN and worst -1 for
+ *     every scenario of the problem; everything else is still computed;
+ *     the maxima of |e_lat|, |e_lon|, |e_th| and |delta - dr| are updated; end position error = hypot(e_lon, e_lat)
+ *     and end |e_th| are those of the last pose the scenario reached;
+ *     if not hypot(e_lon, e_lat) <= abort_dist: DIVERGED, and the scenario stops at this pose (included).
+ *   Control for tick k -> k + 1 (only while k + 1 < np), r+ = ref(k + 1), g = -1 if vr+ < 0, else +1:
+ *     v_des = clamp(vr+ - k_lon e_lon, +-MAXV)               (a set-point limit: it sets no flag)
+ *     a     = clamp((v_des - v) / dt, +-MAXACC)               bites -> SAT_ACC
+ *     d_des = clamp((dr+ - k_lat e_lat) - (g k_yaw) e_th, +-MAXSTEER)   bites -> SAT_STEER
+ *     w     = clamp((d_des - delta) / dt, +-MAXSR)            bites -> SAT_RATE
+ *     Why these signs.  Near the reference e_lat' = v e_th and e_th' = v (delta - dr) / L, so with
+ *     delta - dr = -k_lat e_lat - g k_yaw e_th and g = sign(v) the error dynamics are
+ *       [e_lat; e_th]' = [[0, v], [-v k_lat / L, -|v| k_yaw / L]] [e_lat; e_th]:
+ *     trace -|v| k_yaw / L < 0 and determinant v^2 k_lat / L > 0 in both gears, i.e. stable, with natural frequency
+ *     |v| sqrt(k_lat / L) and damping ratio k_yaw / (2 sqrt(k_lat L)).  Without g the yaw term would feed back
+ *     positively in reverse.
+ *   Plant for tick k -> k + 1: P = plant_substeps midpoint-rule steps of hp = dt / P with a and w held:
+ *     F(q) = the audit's kin at (x, y, (1 - slip) v, theta, delta + steer_bias) with controls (a, w), its heading
+ *     component multiplied by yaw_gain;  q_mid = q + (0.5 hp) F(q);  q <- q + hp F(q_mid).
+ *     The midpoint rule is used whatever the NLP's discretisation: the plant is the truth model.  After the P steps
+ *     delta = clamp(delta, +-MAXSTEER) (it guards rounding and sets no flag).
+ *   The plant is kinematic: no tyre dynamics, no actuator lag beyond the rate limit, no sensor noise; slip and
+ *   yaw_gain are two constant factors.  A clear rollout is evidence, not a guarantee.
+ *   One wavefront per problem, one lane per scenario, one launch.  The device equals a serial evaluation bit for
+ *   bit: every lane's rollout is serial, and everything across lanes is a min with an index or a count. */
+#define HTP_TRACK_MAX_N HTP_AUDIT_MAX_N
+#define HTP_TRACK_NDIST 6            /* lat0, lon0, yaw0, steer_bias, slip, yaw_gain */
+#define HTP_TRACK_MAX_SCENARIOS 4096
+#define HTP_TRACK_MAX_SUBSTEPS 16
+#define HTP_TRACK_NREF 5             /* xr, yr, vr, thr, dr */
+enum {                               /* double metrics[batch][R][HTP_TRACK_NMETRIC] */
+  HTP_TRACK_CLEARANCE = 0,           /* min clearance over the poses reached */
+  HTP_TRACK_MAX_ELAT,                /* max |e_lat| */
+  HTP_TRACK_MAX_ELON,                /* max |e_lon| */
+  HTP_TRACK_MAX_ETH,                 /* max |e_th| */
+  HTP_TRACK_END_POS,                 /* hypot(e_lon, e_lat) at the last pose reached */
+  HTP_TRACK_END_ETH,                 /* |e_th| at the last pose reached */
+  HTP_TRACK_MAX_STEER_DEV,           /* max |delta - dr| */
+  HTP_TRACK_SAT_SHARE,               /* control ticks with a biting a, d_des or w clamp / control ticks taken; 0 if none */
+  HTP_TRACK_NMETRIC
+};
+enum {                               /* int32 flags[batch][R]; bit b is tally column b */
+  HTP_TRACK_COLLISION = 1,           /* clearance < 0 */
+  HTP_TRACK_MARGIN = 2,              /* clearance < params[HTP_P_DMIN] - margin_tol */
+  HTP_TRACK_SAT_STEER = 4,
+  HTP_TRACK_SAT_RATE = 8,
+  HTP_TRACK_SAT_ACC = 16,
+  HTP_TRACK_DIVERGED = 32,
+  HTP_TRACK_TRUNCATED = 64,
+  HTP_TRACK_NONFINITE = 128,
+  HTP_TRACK_BAD_POLYTOPE = 256,
+  HTP_TRACK_BAD_TIME = 512
+};
+#define HTP_TRACK_NFLAG 10
+typedef struct {
+  double dt;                         /* control period, finite and > 0 */
+  int32_t max_ticks;                 /* poses of storage per problem, >= 2 */
+  int32_t plant_substeps;            /* 1 .. HTP_TRACK_MAX_SUBSTEPS */
+  double k_lat, k_yaw, k_lon;        /* finite and >= 0 */
+  double abort_dist;                 /* > 0 (may be infinite) */
+  double margin_tol;                 /* finite and >= 0 */
+  int32_t R;                         /* scenarios, 1 .. HTP_TRACK_MAX_SCENARIOS */
+  const double* scenarios;           /* [R][HTP_TRACK_NDIST], shared by the batch */
+} htp_obca_track_opts;
+typedef struct {
+  double* metrics;          /* [batch][R][HTP_TRACK_NMETRIC] */
+  int32_t* worst;           /* [batch][R][3] tick, obstacle, body of HTP_TRACK_CLEARANCE */
+  int32_t* flags;           /* [batch][R] HTP_TRACK_* bits */
+  int32_t* tally;           /* [batch][HTP_TRACK_NFLAG] scenarios carrying each flag */
+  int32_t* worst_scenario;  /* [batch] argmin of the clearance metric over the scenarios, ties to the lowest; -1 if no
+                               scenario has a clearance */
+  double* tick_clearance;   /* nullable [batch][max_ticks]: per pose the min of clearance_k over the scenarios that
+                               reached it (+inf if none did, NaN with BAD_POLYTOPE); entries at or beyond np are
+                               never written */
+  double* reference;        /* nullable [batch][max_ticks][HTP_TRACK_NREF]: ref(k), k < np; the rest never written */
+} htp_obca_track_result;
+/* API errors (-1 with a "[track]" message, nothing launched): a null required argument, N < 2 or > HTP_TRACK_MAX_N,
+ * dt not finite or <= 0, max_ticks < 2, plant_substeps outside 1..16, R < 1 or > 4096, a negative or non-finite
+ * gain or margin_tol, abort_dist not > 0, an edge count outside 3..8.  batch == 0 returns 0.  Nothing beyond the
+ * batch is ever written. */
+/* host pointers, synchronous; only [X | U | tau] of every x row is uploaded; the entries of tick_clearance and
+ * reference that are never written keep the caller's values */
+int htp_obca_track_batch(htp_ctx* ctx, const htp_obca_batch* in, const double* x, const htp_obca_track_opts* opts,
+                         htp_obca_track_result* out);
+/* device pointers (opts->scenarios too), enqueued on `stream`, not synchronised: behind htp_obca_solve_batch_device
+ * (and the audit or the repair) on the same stream it rolls that solve's out->x without a host round trip */
+int htp_obca_track_batch_device(htp_ctx* ctx, const htp_obca_batch* in, const double* x,
+                                const htp_obca_track_opts* opts, htp_obca_track_result* out, void* stream);
+/* duration (ms) of the last track kernel (hipEvents on its stream) */
+double htp_obca_track_last_ms(htp_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * Warm start -> OBCA initial guess (R/obca_py/util.py get_init_ref_path :62-113
  * with cubic_spline.calc_spline_course :92-112): split at gear changes,
  * re-spline every segment over arc length at ds, v = gear * desired_v,
