@@ -138,6 +138,19 @@ HTP_HD inline void sincos(double x, double& s, double& c) {
 #ifndef HTP_SWEEP_U
 #define HTP_SWEEP_U 8
 #endif
+// The step's vector passes fused (1) or as in round 6 (0); every element by the same expression and every per-lane
+// reduction in the same ascending order, so the same doubles:
+//  * build_newton_rhs computes the barrier gradient inside its own n- and md-sweeps (no grad_barrier pass that
+//    writes gbx / gbs only for the next sweep to read them back with gf);
+//  * the Newton right-hand side's x part is written once into sx, where the KKT solve, the fused right-hand side
+//    of the factor sweep and a later second-order correction read it; the barrier gradient takes xt (free until
+//    the first trial point), and the per-iteration copy sx <- xt goes;
+//  * newton_gbd, detect_tiny_step and the line search's first frac_primal share one sweep per vector length
+//    (step_scan), each with its own accumulator;
+//  * accept_step writes c, d from the accepted trial's ct, dt inside its mc- and md-sweeps (no trailing copies).
+#ifndef HTP_STEP_FUSE
+#define HTP_STEP_FUSE 1
+#endif
 #define HTP_PRAGMA_(x) _Pragma(#x)
 #define HTP_PRAGMA(x) HTP_PRAGMA_(x)
 #define HTP_UNROLL HTP_PRAGMA(unroll HTP_UNROLL_N)
@@ -1328,6 +1341,12 @@ struct ObcaSolver {
   }
 
   HTP_HD HTP_FI gd* A(int64_t off) const { return (gd*)(ws + off); }
+  // x part of the Newton right-hand side, and the barrier gradient's x part (HTP_STEP_FUSE: roles swapped)
+  HTP_HD HTP_FI gd* nrx() const { return A(HTP_STEP_FUSE ? L.sx : L.xt); }
+  HTP_HD HTP_FI gd* gbx_arr() const { return A(HTP_STEP_FUSE ? L.xt : L.sx); }
+#ifdef HTP_TEST_STATS  // tests only: most pivoted local blocks in one factor sweep, second-order corrections taken
+  int stat_piv_max = 0, stat_piv_sweeps = 0, stat_soc = 0;
+#endif
   HTP_HD HTP_FI static const gd* gp(const double* p) { return (const gd*)p; }
   // a wave-uniform pointer as the compiler's uniform value (scalar registers on the device)
   template <class T>
@@ -2521,7 +2540,7 @@ struct ObcaSolver {
           // the fused right-hand side's loads before the block's first store (a load waits for earlier stores)
           if (fuse_rhs) {   // the Newton step's right-hand side (kkt_solve's local_rhs_sweep, fused)
             double v[NL], q3;
-            local_rhs_vec<EN, EM>(p, B, A(L.xt), A(L.rs), A(L.rc), A(L.rd), v, q3);
+            local_rhs_vec<EN, EM>(p, B, nrx(), A(L.rs), A(L.rc), A(L.rd), v, q3);
             B.solve(v);
             for (int k = 0; k < 6; ++k) PS[6 * p + k] = B.Hpp[k] - S[k];
             local_rhs_out<EN, EM>(p, B, v, q3, A(L.pairR));
@@ -2532,7 +2551,7 @@ struct ObcaSolver {
           for (int k = 0; k < 6; ++k) PS[6 * p + k] = B.Hpp[k] - S[k];
           if (fuse_rhs) {   // the Newton step's right-hand side (kkt_solve's local_rhs_sweep, fused)
             double v[NL], q3;
-            local_rhs_vec<EN, EM>(p, B, A(L.xt), A(L.rs), A(L.rc), A(L.rd), v, q3);
+            local_rhs_vec<EN, EM>(p, B, nrx(), A(L.rs), A(L.rc), A(L.rd), v, q3);
             B.solve(v);
             local_rhs_out<EN, EM>(p, B, v, q3, A(L.pairR));
           }
@@ -2552,6 +2571,10 @@ struct ObcaSolver {
       npiv += cnt;
     }
     c.sync();
+#ifdef HTP_TEST_STATS
+    if (npiv > stat_piv_max) stat_piv_max = npiv;
+    if (npiv > 0) ++stat_piv_sweeps;
+#endif
 #ifdef HTP_LPROF
     const long long lt1 = c.clock();
     HTP_LP1(0, lt1 - lt0);
@@ -2589,7 +2612,7 @@ struct ObcaSolver {
               }
             }
           } else if (!done) {
-            local_rhs_vec<EN, EM>(p, B, A(L.xt), A(L.rs), A(L.rc), A(L.rd), v, q3);
+            local_rhs_vec<EN, EM>(p, B, nrx(), A(L.rs), A(L.rc), A(L.rd), v, q3);
           } else {
             local_rhs_out<EN, EM>(p, B, v, q3, A(L.pairR));
           }
@@ -2605,7 +2628,7 @@ struct ObcaSolver {
         double Vp[4 * NL], q3 = 0.0;
         for (int col = 0; col < 3; ++col)
           for (int r = 0; r < NL; ++r) Vp[col * NL + r] = B.B[r][col];
-        if (fuse_rhs) local_rhs_vec<EN, EM>(p, B, A(L.xt), A(L.rs), A(L.rc), A(L.rd), Vp + 3 * NL, q3);
+        if (fuse_rhs) local_rhs_vec<EN, EM>(p, B, nrx(), A(L.rs), A(L.rc), A(L.rd), Vp + 3 * NL, q3);
         local_pivoted<EN, EM>(p, ls, dw, dc, Vp, fuse_rhs ? 4 : 3, pn);
         if (fuse_rhs) local_rhs_out<EN, EM>(p, B, Vp + 3 * NL, q3, A(L.pairR));
         for (int col = 0; col < 3; ++col)
@@ -4902,7 +4925,7 @@ struct ObcaSolver {
         // the Newton step's rhs is known here (fused local sweep: pairR is this trial's): build V and run the
         // solve's backward pass with the factor
         const bool fb = fuse_rhs && !PT && !ric_relax && !ls;
-        if (fb) { build_stage_rhs(ls, dw, dc, A(L.xt), A(L.rc)); c.sync(); }
+        if (fb) { build_stage_rhs(ls, dw, dc, nrx(), A(L.rc)); c.sync(); }
         bad = riccati_factor_mfma(dc, fb);
         bwd_ready = fb && !bad;
 #else
@@ -5970,12 +5993,44 @@ struct ObcaSolver {
   // Newton right-hand side at the current point: rx (into xt), rs, rc, rd[, rRx] ; gbx (sx), gbs (ss)
   // returns the directional-derivative factors via gBD once the step exists (newton_gbd)
   HTP_HD HTP_FI void build_newton_rhs(const gd* gl) {
-    gd* gbx = A(L.sx); gd* gbs = A(L.ss);
-    grad_barrier(mu, gbx, gbs);
-    gd* rx = A(L.xt);
+    gd* gbx = gbx_arr(); gd* gbs = A(L.ss);
+    gd* rx = nrx();
     gd* rs_ = A(L.rs); gd* rc = A(L.rc); gd* rd = A(L.rd);
     const gd* gf = A(L.gf); const gd* yd = A(L.yd); const gd* cc = A(L.c); const gd* dd = A(L.d);
     const gd* s = A(L.s);
+    if (HTP_STEP_FUSE) {   // grad_barrier's expressions inside the right-hand side's own sweeps
+      const gd* x = A(L.x); const gd* xL = A(L.xL); const gd* xU = A(L.xU);
+      const gd* dL = A(L.dL); const gd* dU = A(L.dU);
+      const double mu_ = mu, kd = o.kappa_d * mu_;
+      {
+        double x_[SW_U], xl_[SW_U], xu_[SW_U], g_[SW_U], a_[SW_U];
+        sweep(D.n, [&](int q, int k) { x_[k] = x[q]; xl_[k] = xL[q]; xu_[k] = ubx(q) ? (double)xU[q] : HTP_INF; g_[k] = gf[q]; a_[k] = gl[q]; },
+              [&](int q, int k) {
+                const bool hl = finite_(xl_[k]), hu = finite_(xu_[k]);
+                double g = g_[k];
+                if (hl) g -= mu_ / (x_[k] - xl_[k]);
+                if (hu) g += mu_ / (xu_[k] - x_[k]);
+                if (hl && !hu) g += kd;
+                if (hu && !hl) g -= kd;
+                gbx[q] = g;
+                rx[q] = -(a_[k] - g_[k] + g);
+              });
+      }
+      {
+        double s_[SW_U], dl_[SW_U], du_[SW_U], b_[SW_U], d_[SW_U];
+        sweep(D.md, [&](int r, int k) { s_[k] = s[r]; dl_[k] = dL[r]; du_[k] = ubs(r) ? (double)dU[r] : HTP_INF; b_[k] = yd[r]; d_[k] = dd[r]; },
+              [&](int r, int k) {
+                const bool hu = finite_(du_[k]);
+                double g = -mu_ / (s_[k] - dl_[k]);
+                if (hu) g += mu_ / (du_[k] - s_[k]);
+                else g += kd;
+                gbs[r] = g;
+                rs_[r] = -(g - b_[k]);
+                rd[r] = -(d_[k] - s_[k]);
+              });
+      }
+    } else {
+    grad_barrier(mu, gbx, gbs);
     {
       double a_[SW_U], b_[SW_U], g_[SW_U];
       sweep(D.n, [&](int q, int k) { a_[k] = gl[q]; b_[k] = gf[q]; g_[k] = gbx[q]; },
@@ -5985,6 +6040,7 @@ struct ObcaSolver {
       double a_[SW_U], b_[SW_U], d_[SW_U], s_[SW_U];
       sweep(D.md, [&](int r, int k) { a_[k] = gbs[r]; b_[k] = yd[r]; d_[k] = dd[r]; s_[k] = s[r]; },
             [&](int r, int k) { rs_[r] = -(a_[k] - b_[k]); rd[r] = -(d_[k] - s_[k]); });
+    }
     }
     {
       double a_[SW_U];
@@ -6002,7 +6058,7 @@ struct ObcaSolver {
   }
   // gradient of the barrier function along (dx, ds[, dR]); gbx, gbs must be current (sx, ss)
   HTP_HD HTP_FI double newton_gbd(const gd* dx, const gd* ds, const gd* dR) {
-    const gd* gbx = A(L.sx); const gd* gbs = A(L.ss);
+    const gd* gbx = gbx_arr(); const gd* gbs = A(L.ss);
     double g = 0.0;
     {
       double a_[SW_U], b_[SW_U];
@@ -6029,6 +6085,8 @@ struct ObcaSolver {
     const gd* dvL = A(L.dvL); const gd* dvU = A(L.dvU);
     gd* xL = A(L.xL); gd* xU = A(L.xU);
     gd* dL = A(L.dL); gd* dU = A(L.dU);
+    gd* cc_ = A(L.c); gd* dd_ = A(L.d);            // HTP_STEP_FUSE: c, d <- the accepted trial's ct, dt in the
+    const gd* ctr = A(L.ct); const gd* dtr = A(L.dt);   // mc- and md-sweeps below
     const double ks = o.kappa_sigma;
     {
       double x_[SW_U], d_[SW_U], xl_[SW_U], xu_[SW_U], zl_[SW_U], zu_[SW_U], dzl_[SW_U], dzu_[SW_U];
@@ -6052,12 +6110,14 @@ struct ObcaSolver {
             });
     }
     {
-      double s_[SW_U], d_[SW_U], y_[SW_U], dy_[SW_U], vl_[SW_U], dvl_[SW_U], dl_[SW_U], vu_[SW_U], dvu_[SW_U], du_[SW_U];
+      double s_[SW_U], d_[SW_U], y_[SW_U], dy_[SW_U], vl_[SW_U], dvl_[SW_U], dl_[SW_U], vu_[SW_U], dvu_[SW_U], du_[SW_U], t_[SW_U];
       sweep(D.md, [&](int r, int k) { s_[k] = s[r]; d_[k] = ds[r]; y_[k] = yd[r]; dy_[k] = dyd[r]; vl_[k] = vL[r];
-                                       dvl_[k] = dvL[r]; dl_[k] = dL[r]; vu_[k] = ubs(r) ? (double)vU[r] : 0.0; dvu_[k] = ubs(r) ? (double)dvU[r] : 0.0; du_[k] = ubs(r) ? (double)dU[r] : HTP_INF; },
+                                       dvl_[k] = dvL[r]; dl_[k] = dL[r]; vu_[k] = ubs(r) ? (double)vU[r] : 0.0; dvu_[k] = ubs(r) ? (double)dvU[r] : 0.0; du_[k] = ubs(r) ? (double)dU[r] : HTP_INF;
+                                       if (HTP_STEP_FUSE) t_[k] = dtr[r]; },
             [&](int r, int k) {
               const double sn = s_[k] + a_primal * d_[k];
               s[r] = sn;
+              if (HTP_STEP_FUSE) dd_[r] = t_[k];
               yd[r] = y_[k] + a_primal * dy_[k];
               {
                 const double v0 = sn - dl_[k], v = safe_slack(v0, vl_[k], dl_[k], mu);
@@ -6074,9 +6134,9 @@ struct ObcaSolver {
             });
     }
     {
-      double y_[SW_U], dy_[SW_U];
-      sweep(D.mc, [&](int r, int k) { y_[k] = yc[r]; dy_[k] = dyc[r]; },
-            [&](int r, int k) { yc[r] = y_[k] + a_primal * dy_[k]; });
+      double y_[SW_U], dy_[SW_U], t_[SW_U];
+      sweep(D.mc, [&](int r, int k) { y_[k] = yc[r]; dy_[k] = dyc[r]; if (HTP_STEP_FUSE) t_[k] = ctr[r]; },
+            [&](int r, int k) { yc[r] = y_[k] + a_primal * dy_[k]; if (HTP_STEP_FUSE) cc_[r] = t_[k]; });
     }
     if (rs) {
       gd* R = A(L.R); gd* zR = A(L.zR);
@@ -6091,8 +6151,10 @@ struct ObcaSolver {
             });
     }
     c.sync();
-    copy_arr(A(L.c), A(L.ct), D.mc);
-    copy_arr(A(L.d), A(L.dt), D.md);
+    if (!HTP_STEP_FUSE) {
+      copy_arr(A(L.c), A(L.ct), D.mc);
+      copy_arr(A(L.d), A(L.dt), D.md);
+    }
   }
 
   // IpBacktrackingLineSearch::DetectTinyStep (x includes R in the restoration phase)
@@ -6136,13 +6198,83 @@ struct ObcaSolver {
     return true;
   }
 
+  // HTP_STEP_FUSE: newton_gbd, detect_tiny_step and frac_primal of the Newton step at the current point in one
+  // sweep per vector length.  Each quantity keeps its own accumulator and its own order of vectors (the sum n, md,
+  // nR; the step maxima n, nR and md, mc; the fraction n, md, nR), so each is the double its own pass returns.
+  // The fraction to the boundary stays valid for the line search (frac_primal_step) until the point or the step
+  // changes.
+  double amax_c = 1.0;
+  bool amax_ok = false;
+  HTP_HD HTP_FI void step_scan(const gd* dx, const gd* ds, const gd* dyc, const gd* dyd, const gd* dR, double& gbd,
+                               bool& tiny) {
+    const gd* x = A(L.x); const gd* xL = A(L.xL); const gd* xU = A(L.xU);
+    const gd* s = A(L.s); const gd* dL = A(L.dL); const gd* dU = A(L.dU);
+    const gd* cc = A(L.c); const gd* dd = A(L.d);
+    const gd* gbx = gbx_arr(); const gd* gbs = A(L.ss);
+    double g = 0.0, a = 1.0, mx = 0.0, ms = 0.0, my = 0.0, pv = 0.0;
+    {
+      double x_[SW_U], xl_[SW_U], xu_[SW_U], d_[SW_U], b_[SW_U];
+      sweep(D.n, [&](int q, int k) { b_[k] = gbx[q]; d_[k] = dx[q]; x_[k] = x[q]; xl_[k] = xL[q]; xu_[k] = ubx(q) ? (double)xU[q] : HTP_INF; },
+            [&](int, int k) {
+              g += b_[k] * d_[k];
+              mx = nmax(mx, dabs(d_[k]) / (1.0 + dabs(x_[k])));
+              if (finite_(xl_[k]) && d_[k] < 0) a = dmin(a, -tau * (x_[k] - xl_[k]) / d_[k]);
+              if (finite_(xu_[k]) && -d_[k] < 0) a = dmin(a, -tau * (xu_[k] - x_[k]) / (-d_[k]));
+            });
+    }
+    {
+      double s_[SW_U], dl_[SW_U], du_[SW_U], d_[SW_U], b_[SW_U], y_[SW_U], v_[SW_U];
+      sweep(D.md, [&](int r, int k) { b_[k] = gbs[r]; d_[k] = ds[r]; s_[k] = s[r]; dl_[k] = dL[r]; du_[k] = ubs(r) ? (double)dU[r] : HTP_INF; y_[k] = dyd[r]; v_[k] = dd[r]; },
+            [&](int, int k) {
+              g += b_[k] * d_[k];
+              ms = nmax(ms, dabs(d_[k]) / (1.0 + dabs(s_[k])));
+              my = nmax(my, dabs(y_[k]));
+              pv = nmax(pv, dabs(v_[k] - s_[k]));
+              if (d_[k] < 0) a = dmin(a, -tau * (s_[k] - dl_[k]) / d_[k]);
+              if (finite_(du_[k]) && -d_[k] < 0) a = dmin(a, -tau * (du_[k] - s_[k]) / (-d_[k]));
+            });
+    }
+    if (rs) {
+      const gd* R = A(L.R);
+      double b_[SW_U], d_[SW_U], r_[SW_U];
+      sweep(nR, [&](int j, int k) { b_[k] = np_grad_barrier(j, R, mu); d_[k] = dR[j]; r_[k] = R[j]; },
+            [&](int, int k) {
+              g += b_[k] * d_[k];
+              mx = nmax(mx, dabs(d_[k]) / (1.0 + dabs(r_[k])));
+              if (d_[k] < 0) a = dmin(a, -tau * r_[k] / d_[k]);
+            });
+    }
+    {
+      double y_[SW_U], c_[SW_U];
+      sweep(D.mc, [&](int r, int k) { y_[k] = dyc[r]; c_[k] = cc[r]; },
+            [&](int, int k) {
+              my = nmax(my, dabs(y_[k]));
+              pv = nmax(pv, dabs(c_[k]));
+            });
+    }
+    gbd = c.sum(g);
+    amax_c = c.minv(a);
+    amax_ok = true;
+    tiny = false;
+    if (o.tiny_step_tol == 0.0) return;
+    // a NaN anywhere in the step is not a tiny step (the wave maxima below drop NaN operands)
+    if (HTP_NAN_GUARD && c.isum((mx == mx && ms == ms && my == my && pv == pv) ? 0 : 1) > 0) return;
+    mx = c.maxv(mx); ms = c.maxv(ms); my = c.maxv(my); pv = c.maxv(pv);
+    tiny = !(mx > o.tiny_step_tol || ms > o.tiny_step_tol) && !(my >= o.tiny_step_y_tol) && !(pv > 1e-4);
+  }
+  // frac_primal of the Newton step at the current point: step_scan's value while it holds
+  HTP_HD HTP_FI double frac_primal_step(const gd* dx, const gd* ds, const gd* dR) const {
+    if (HTP_STEP_FUSE && amax_ok) return amax_c;
+    return frac_primal(dx, ds, dR);
+  }
+
   // ---------------------------------------------------------- watchdog
   // stores the current point, its constraint values, the step and the reference values
   HTP_COLD HTP_HD void start_watchdog(double th, double ph, double gbd, double dw, double dc) {
     ls_.in_wd = 1;
     ls_.wd_th = th; ls_.wd_ph = ph; ls_.wd_gbd = gbd; ls_.wd_dw = dw; ls_.wd_dc = dc;
     ls_.wd_trial = 0;
-    ls_.wd_alpha = frac_primal(A(L.dx), A(L.ds), A(L.dR));
+    ls_.wd_alpha = frac_primal_step(A(L.dx), A(L.ds), A(L.dR));
     copy_arr(A(L.wx), A(L.x), D.n); copy_arr(A(L.ws), A(L.s), D.md);
     copy_arr(A(L.wyc), A(L.yc), D.mc); copy_arr(A(L.wyd), A(L.yd), D.md);
     copy_arr(A(L.wzL), A(L.zL), D.n); copy_arr(A(L.wzU), A(L.zU), D.n);
@@ -6155,6 +6287,7 @@ struct ObcaSolver {
   // back to the stored point and step; its gradients, Newton rhs and the stored matrix (for SOC)
   HTP_COLD HTP_HD void stop_watchdog() {
     ls_.in_wd = 0;
+    amax_ok = false;   // another point and another step
     copy_arr(A(L.x), A(L.wx), D.n); copy_arr(A(L.s), A(L.ws), D.md);
     copy_arr(A(L.yc), A(L.wyc), D.mc); copy_arr(A(L.yd), A(L.wyd), D.md);
     copy_arr(A(L.zL), A(L.wzL), D.n); copy_arr(A(L.zU), A(L.wzU), D.n);
@@ -6182,7 +6315,7 @@ struct ObcaSolver {
     gd* x = A(L.x); gd* s = A(L.s);
     gd* dx = A(L.dx); gd* ds = A(L.ds); gd* dyc = A(L.dyc); gd* dyd = A(L.dyd); gd* dR = A(L.dR);
     const gd* cc = A(L.c); const gd* dd = A(L.d);
-    const double alpha_max = frac_primal(dx, ds, dR);
+    const double alpha_max = frac_primal_step(dx, ds, dR);
     double alpha_min;
     if (ls_.in_wd) {
       alpha_min = alpha_max;
@@ -6235,6 +6368,10 @@ struct ObcaSolver {
           trial_values(xt, st, Rt, th_soc, ph_soc);
           if (check_trial(th, ph, gbd, a_test, th_soc, ph_soc)) {
             soc_ok = true; alpha = a_soc; th_t = th_soc; ph_t = ph_soc;
+            amax_ok = false;   // the step becomes the corrected one
+#ifdef HTP_TEST_STATS
+            ++stat_soc;
+#endif
             copy_arr(dx, sx, D.n); copy_arr(ds, ss_, D.md); copy_arr(dyc, syc, D.mc); copy_arr(dyd, syd, D.md);
             if (rs) copy_arr(dR, sR, nR);
             break;
@@ -6267,7 +6404,7 @@ struct ObcaSolver {
   HTP_COLD HTP_HD int try_soft_resto_step(double th, double ph, double gbd, const gd* gl) {
     const gd* dx = A(L.dx); const gd* ds = A(L.ds); const gd* dyc = A(L.dyc); const gd* dyd = A(L.dyd);
     const gd* dR = A(L.dR);
-    const double ap = frac_primal(dx, ds, dR);
+    const double ap = frac_primal_step(dx, ds, dR);
     const double ad = dual_steps(dx, ds, dR);
     const double a = dmin(ap, ad);
     set_trial(a, dx, ds, dR);
@@ -6590,7 +6727,7 @@ struct ObcaSolver {
       } else {
         if (dw > 0.0) dw_last = dw;
         HTP_TRACE("[trace] factored dw=%g\n", dw);
-        kkt_solve(false, dw, dc, A(L.xt), A(L.rs), A(L.rc), A(L.rd), dx, ds, dyc, dyd, A(L.rRx), dR, rhs_done);
+        kkt_solve(false, dw, dc, nrx(), A(L.rs), A(L.rc), A(L.rd), dx, ds, dyc, dyd, A(L.rRx), dR, rhs_done);
       }
       // ---- line search (IpBacktrackingLineSearch::FindAcceptableTrialPoint)
       long long tls = c.clock();
@@ -6600,22 +6737,26 @@ struct ObcaSolver {
       double theta = (theta_cache >= 0.0) ? theta_cache : theta_of(cc, dd, s);
       bool goto_resto = ls_.fallback != 0;
       ls_.fallback = 0;
-      double gbd = goto_resto ? 0.0 : newton_gbd(dx, ds, dR);
+      amax_ok = false;
+      double gbd = 0.0;
+      bool tiny_scan = false;
+      if (HTP_STEP_FUSE) { if (!goto_resto) step_scan(dx, ds, dyc, dyd, dR, gbd, tiny_scan); }
+      else gbd = goto_resto ? 0.0 : newton_gbd(dx, ds, dR);
       // A step with a NaN / infinite entry (a KKT system solved beyond floating-point range): IPOPT cuts back on
       // every trial-point evaluation error and so never takes such a step -- its line search fails and the
       // restoration phase is called, which is where this goes directly.
       if (HTP_NAN_GUARD && !goto_resto && !(dabs(gbd) < HTP_INF)) { goto_resto = true; gbd = 0.0; }
-      copy_arr(A(L.sx), A(L.xt), D.n);  // keep the Newton rhs (x part) for second-order corrections
+      if (!HTP_STEP_FUSE) copy_arr(A(L.sx), A(L.xt), D.n);  // keep the Newton rhs (x part) for second-order corrections
       double rth = theta, rph = phi, rgbd = gbd;
       if (ls_.in_wd) { rth = ls_.wd_th; rph = ls_.wd_ph; rgbd = ls_.wd_gbd; }
       bool accept = false;
       int n_steps = 0;
       double a_primal = 0.0, a_test = 0.0, ph_t = 0.0, th_t = 0.0;
       double cdw = dw, cdc = dc;
-      bool tiny = !goto_resto && detect_tiny_step(dx, ds, dyc, dyd, dR);
+      bool tiny = !goto_resto && (HTP_STEP_FUSE ? tiny_scan : detect_tiny_step(dx, ds, dyc, dyd, dR));
       if (ls_.in_wd && (goto_resto || tiny)) {
         stop_watchdog();
-        copy_arr(A(L.sx), A(L.xt), D.n);
+        if (!HTP_STEP_FUSE) copy_arr(A(L.sx), A(L.xt), D.n);
         theta = rth; phi = rph; cdw = ls_.wd_dw; cdc = ls_.wd_dc;
         goto_resto = tiny = false;
       }
@@ -6623,7 +6764,7 @@ struct ObcaSolver {
           ls_.wd_short >= o.watchdog_shortened_iter_trigger)
         start_watchdog(theta, phi, gbd, dw, dc);
       if (tiny) {
-        a_primal = frac_primal(dx, ds, dR);
+        a_primal = frac_primal_step(dx, ds, dR);
         set_trial(a_primal, dx, ds, dR);
         trial_values(A(L.xt), A(L.st), A(L.Rt), th_t, ph_t);
         if (ls_.tiny_last) ls_.tiny_flag = 1;
@@ -6649,7 +6790,7 @@ struct ObcaSolver {
               if (accept) { ls_.in_wd = 0; break; }
               if (++ls_.wd_trial > o.watchdog_trial_iter_max) {
                 stop_watchdog();
-                copy_arr(A(L.sx), A(L.xt), D.n);
+                if (!HTP_STEP_FUSE) copy_arr(A(L.sx), A(L.xt), D.n);
                 rth = ls_.wd_th; rph = ls_.wd_ph; rgbd = ls_.wd_gbd;
                 theta = rth; phi = rph; cdw = ls_.wd_dw; cdc = ls_.wd_dc;
                 skip = true;

@@ -2,7 +2,10 @@
 kernel time, solves/s, bit-identity against the first variant, and the
 per-phase cycle shares; variants built with -DHTP_KKT_PROF report the KKT
 solve's sub-phases (local rhs sweep, stage Riccati solve, local back sweep) in
-the last three slots.   python tools/ab_phase.py CFG B name1 name2 ..."""
+the last three slots.  Every variant's later runs must equal its first run bit for
+bit (solution, objective, status, iterations): a run that does not ends the tool.
+
+    python tools/ab_phase.py [--rounds R] CFG B name1 name2 ...      (R >= 2, default 2)"""
 import sys
 
 import numpy as np
@@ -11,26 +14,45 @@ sys.path.insert(0, ".")
 from headland_trajectory_planning_amd import _native  # noqa: E402
 import bench  # noqa: E402
 
-cfg, B = sys.argv[1], int(sys.argv[2])
-names = sys.argv[3:]
+args = sys.argv[1:]
+rounds = 2
+if args and args[0] == "--rounds":
+    rounds = max(2, int(args[1]))
+    args = args[2:]
+cfg, B = args[0], int(args[1])
+names = args[2:]
 pk = _native.PackedBatch(bench.make_batch(list(range(B)), cfg, 16))
 ctxs = {}
 for n in names:
     path = _native.LIB_PATH if n == "base" else _native.LIB_PATH.replace("libhtp.so", f"libhtp_{n}.so")
     ctxs[n] = _native.Context(0, lib=_native.load(path))
 ref = None
-for rnd in range(2):
+first = {}
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+for rnd in range(rounds):
     for k, ctx in ctxs.items():
         r = ctx.solve(pk)
         ms = ctx.last_kernel_ms()
+        if k not in first:
+            first[k] = r
+        else:   # run-to-run determinism of each variant, bitwise
+            f = first[k]
+            assert np.array_equal(_bits(f.x), _bits(r.x)) and np.array_equal(_bits(f.objective), _bits(r.objective)) \
+                and np.array_equal(f.status, r.status) and np.array_equal(f.iterations, r.iterations), \
+                f"variant {k}: run {rnd} differs from its run 0"
         ok = ""
         if ref is None:
             ref = r
         else:
-            ok = f" max|dx|={np.max(np.abs(ref.x - r.x)):.2e} status_eq={np.array_equal(ref.status, r.status)} " \
+            ok = f" bits_eq={np.array_equal(_bits(ref.x), _bits(r.x))} max|dx|={np.max(np.abs(ref.x - r.x)):.2e} status_eq={np.array_equal(ref.status, r.status)} " \
                  f"iters_eq={np.array_equal(ref.iterations, r.iterations)}"
         line = f"round {rnd} {k}: kernel {ms:.1f} ms {B / (ms / 1e3):.0f} solves/s iters {r.iterations.mean():.2f}{ok}"
-        if rnd == 1:
+        if rnd == rounds - 1:
             cyc = ctx.last_cycles(B).astype(float)
             tot = cyc[:, 4].sum()
             tail = ["rhs_sweep", "ric_solve", "back_sweep"] if "kprof" in k else ["errors", "linesearch", "update"]

@@ -1,5 +1,6 @@
 """Build A/B variants of libhtp.so with different compile flags for the OBCA
-TU (experiments only; the product library is built by __graft_entry__.build()).
+TU (experiments only; the product library is built by __graft_entry__.build(), whose
+compiler and flags this uses, and whose objects of the other TUs it links: run build() first).
 
     python tools/build_variants.py name1="-DFOO" name2="-DBAR=2" ...
 """
@@ -11,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "headland_trajectory_planning_amd", "csrc")
 PKG = os.path.join(ROOT, "headland_trajectory_planning_amd")
 OBJ = os.path.join(ROOT, "build", "obj")
-HIPCC = "/opt/rocm/bin/hipcc"
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]   # __graft_entry__.build()'s
 
 procs = []
 names = []
