@@ -389,6 +389,99 @@ class TrackResults:
         return d
 
 
+class LqrOpts(ctypes.Structure):  # htp_obca_lqr_opts
+    _fields_ = [(n, ctypes.c_double) for n in (
+        "q_lon", "q_lat", "q_v", "q_th", "q_st", "qf", "r_a", "r_w", "sig0_lon", "sig0_lat", "sig0_v", "sig0_th",
+        "sig0_st", "w_lon", "w_lat", "w_v", "w_th", "w_st", "k_sigma")]
+
+
+class LqrResult(ctypes.Structure):  # htp_obca_lqr_result
+    _fields_ = [(n, ctypes.c_void_p) for n in ("gains", "tube", "metrics", "worst", "flags", "cost_to_go",
+                                               "linearisation")]
+
+
+LQR_METRICS = ("max_sigma_lat", "max_sigma_lon", "max_sigma_theta", "end_sigma_lat", "max_gain", "trace_p0",
+               "ratio_acc", "ratio_rate", "ratio_steer", "ratio_speed")
+LQR_FLAGS = {"AUTHORITY_ACC": 1, "AUTHORITY_RATE": 2, "AUTHORITY_STEER": 4, "AUTHORITY_SPEED": 8, "SINGULAR": 16,
+             "NONFINITE": 32, "BAD_TIME": 64, "BAD_LIMIT": 128}
+LQR_TUBE_COLUMNS = ("sigma_lon", "sigma_lat", "sigma_v", "sigma_theta", "sigma_steer", "sigma_accel",
+                    "sigma_steer_rate")
+LQR_MAX_N = 480
+# Defaults by Bryson's rule (a weight is one over the square of the deviation one is willing to accept): 0.1 m
+# across and 0.2 m along the path, 0.2 m/s, 0.1 rad of heading and 0.2 rad of steering; the controls are weighted
+# in units of their own limits (r = 1: a full-scale control costs as much as one accepted state deviation); the end
+# state counts ten times.  sig0 are the sigmas of track_scenarios; w is a design choice: 1 cm of position and 0.01
+# rad of heading random walk per root second.  k_sigma = 2: a flag where less than two sigma of headroom is left.
+LQR_DEFAULTS = dict(q_lon=1.0 / 0.2 ** 2, q_lat=1.0 / 0.1 ** 2, q_v=1.0 / 0.2 ** 2, q_th=1.0 / 0.1 ** 2,
+                    q_st=1.0 / 0.2 ** 2, qf=10.0, r_a=1.0, r_w=1.0, sig0_lon=0.05, sig0_lat=0.05, sig0_v=0.0,
+                    sig0_th=0.02, sig0_st=0.0, w_lon=1e-4, w_lat=1e-4, w_v=0.0, w_th=1e-4, w_st=0.0, k_sigma=2.0)
+
+
+def lqr_opts(**opts):
+    """htp_obca_lqr_opts: LQR_DEFAULTS overridden by the keywords (the names of the struct's fields)."""
+    unknown = set(opts) - set(LQR_DEFAULTS)
+    if unknown:
+        raise TypeError(f"[htp] lqr: unknown options {sorted(unknown)}")
+    v = {**LQR_DEFAULTS, **opts}
+    return LqrOpts(*(float(v[n]) for n, _ in LqrOpts._fields_))
+
+
+class LqrResults:
+    """Host arrays of one LQR pass: gains [rows, N-1, 2, 5] (u = U_i - K_i (s - X_i)), tube [rows, N, 7]
+    (LQR_TUBE_COLUMNS), metrics [rows, 10] (LQR_METRICS), worst [rows, 2] (node of max_sigma_lat, stage of
+    ratio_rate), flags [rows] (LQR_FLAGS bits), cost_to_go [rows, N, 15] or None (upper triangle of P_i, row-major),
+    linearisation [rows, N-1, 35] or None (A_i, then B_i, row-major).  The arrays are pre-filled with NaN (worst
+    with -1): what a flag leaves unwritten stays so."""
+    METRICS = LQR_METRICS
+    FLAGS = LQR_FLAGS
+
+    def __init__(self, rows, N, cost_to_go=False, linearisation=False):
+        self.N = int(N)
+        self.gains = np.full((rows, self.N - 1, 2, 5), np.nan)
+        self.tube = np.full((rows, self.N, len(LQR_TUBE_COLUMNS)), np.nan)
+        self.metrics = np.full((rows, len(LQR_METRICS)), np.nan)
+        self.worst = np.full((rows, 2), -1, dtype=np.int32)
+        self.flags = np.zeros(rows, dtype=np.int32)
+        self.cost_to_go = np.full((rows, self.N, 15), np.nan) if cost_to_go else None
+        self.linearisation = np.full((rows, self.N - 1, 35), np.nan) if linearisation else None
+
+    def struct(self):
+        r = LqrResult()
+        for n in ("gains", "tube", "metrics", "worst", "flags"):
+            setattr(r, n, getattr(self, n).ctypes.data)
+        r.cost_to_go = None if self.cost_to_go is None else self.cost_to_go.ctypes.data
+        r.linearisation = None if self.linearisation is None else self.linearisation.ctypes.data
+        return r
+
+    def metric(self, name):
+        return self.metrics[:, LQR_METRICS.index(name)]
+
+    def flag_names(self, k):
+        return [n for n, bit in LQR_FLAGS.items() if int(self.flags[k]) & bit]
+
+    def P(self, k, i):
+        """The cost-to-go matrix P_i of problem k as a full symmetric [5, 5]."""
+        if self.cost_to_go is None:
+            raise ValueError("[htp] lqr: no cost_to_go was asked for")
+        m = np.zeros((5, 5))
+        m[np.triu_indices(5)] = self.cost_to_go[k, i]
+        return m + np.triu(m, 1).T
+
+    def as_dict(self, k):
+        d = {n: float(self.metrics[k, j]) for j, n in enumerate(LQR_METRICS)}
+        d["gains"] = self.gains[k].copy()
+        d["tube"] = {n: self.tube[k, :, j].copy() for j, n in enumerate(LQR_TUBE_COLUMNS)}
+        d["worst"] = {"max_sigma_lat": int(self.worst[k, 0]), "ratio_rate": int(self.worst[k, 1])}
+        d["flags"] = self.flag_names(k)
+        d["ok"] = int(self.flags[k]) == 0
+        if self.cost_to_go is not None:
+            d["cost_to_go"] = self.cost_to_go[k].copy()
+        if self.linearisation is not None:
+            d["A"] = self.linearisation[k, :, :25].reshape(-1, 5, 5).copy()
+            d["B"] = self.linearisation[k, :, 25:].reshape(-1, 5, 2).copy()
+        return d
+
+
 class RepairOpts(ctypes.Structure):  # htp_obca_repair_opts
     _fields_ = [("rounds", ctypes.c_int32), ("pad", ctypes.c_double), ("max_raise", ctypes.c_double),
                 ("audit", AuditOpts)]
@@ -565,7 +658,8 @@ EXPORTS = ["htp_obca_sizes", "htp_create", "htp_destroy", "htp_last_error", "htp
            "htp_obca_repair_merge_batch_device", "htp_obca_repair_batch", "htp_obca_repair_batch_device",
            "htp_obca_repair_last_ms",
            "htp_obca_envelope_batch", "htp_obca_envelope_batch_device", "htp_obca_envelope_last_ms",
-           "htp_obca_track_batch", "htp_obca_track_batch_device", "htp_obca_track_last_ms"]
+           "htp_obca_track_batch", "htp_obca_track_batch_device", "htp_obca_track_last_ms",
+           "htp_obca_lqr_batch", "htp_obca_lqr_batch_device", "htp_obca_lqr_last_ms"]
 
 
 def _declare(lib):
@@ -713,6 +807,14 @@ def _declare(lib):
         lib.htp_obca_track_batch_device.restype = ctypes.c_int
         lib.htp_obca_track_last_ms.argtypes = [ctypes.c_void_p]
         lib.htp_obca_track_last_ms.restype = ctypes.c_double
+    if hasattr(lib, "htp_obca_lqr_batch"):   # likewise
+        lib.htp_obca_lqr_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(ObcaBatch), ctypes.c_void_p,
+                                           ctypes.POINTER(LqrOpts), ctypes.POINTER(LqrResult)]
+        lib.htp_obca_lqr_batch.restype = ctypes.c_int
+        lib.htp_obca_lqr_batch_device.argtypes = lib.htp_obca_lqr_batch.argtypes + [ctypes.c_void_p]
+        lib.htp_obca_lqr_batch_device.restype = ctypes.c_int
+        lib.htp_obca_lqr_last_ms.argtypes = [ctypes.c_void_p]
+        lib.htp_obca_lqr_last_ms.restype = ctypes.c_double
     if hasattr(lib, "htp_mfma_f64_probe"):   # absent from libraries built before it (A/B variants of old kernels)
         lib.htp_mfma_f64_probe.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
         lib.htp_mfma_f64_probe.restype = ctypes.c_int
@@ -1716,6 +1818,37 @@ class Context:
 
     def track_last_ms(self):
         return self.lib.htp_obca_track_last_ms(self.ctx)
+
+    def lqr(self, packed, x, cost_to_go=False, linearisation=False, **opts):
+        """Time-varying LQR gains and error tube about decision vectors x [batch, n_var] of `packed` (host buffers)
+        -> LqrResults.  Keywords: the fields of htp_obca_lqr_opts (LQR_DEFAULTS)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (packed.batch, packed.n_var):
+            raise ValueError(f"[htp] lqr: x must be [{packed.batch}, {packed.n_var}], got {x.shape}")
+        res = LqrResults(packed.batch, packed.N, cost_to_go, linearisation)
+        b, r, o = packed.struct(), res.struct(), lqr_opts(**opts)
+        rc = self.lib.htp_obca_lqr_batch(self.ctx, ctypes.byref(b), x.ctypes.data, ctypes.byref(o), ctypes.byref(r))
+        if rc != 0:
+            raise RuntimeError(f"[htp] htp_obca_lqr_batch failed: {self.error()}")
+        return res
+
+    def lqr_device(self, packed, dev_ptrs, x_ptr, out_ptrs, stream=None, lo=None, hi=None, **opts):
+        """Device-resident LQR pass of `packed` (or of its problems [lo, hi)) on `stream`, not synchronised.  x_ptr:
+        device pointer of the [batch, n_var] rows (e.g. a solve's out x); out_ptrs: device pointers gains
+        [batch, N-1, 2, 5], tube [batch, N, 7], metrics [batch, 10], worst [batch, 2], flags [batch] and optionally
+        cost_to_go [batch, N, 15] and linearisation [batch, N-1, 35] (torch tensors' data_ptr())."""
+        b = packed.struct(dev_ptrs) if lo is None else packed.chunk_struct(dev_ptrs, lo, hi)
+        r = LqrResult()
+        for k, v in out_ptrs.items():
+            setattr(r, k, v)
+        o = lqr_opts(**opts)
+        rc = self.lib.htp_obca_lqr_batch_device(self.ctx, ctypes.byref(b), x_ptr, ctypes.byref(o), ctypes.byref(r),
+                                                stream)
+        if rc != 0:
+            raise RuntimeError(f"[htp] htp_obca_lqr_batch_device failed: {self.error()}")
+
+    def lqr_last_ms(self):
+        return self.lib.htp_obca_lqr_last_ms(self.ctx)
 
     def _repair_call(self, name, *args):
         if getattr(self.lib, name)(self.ctx, *args) != 0:

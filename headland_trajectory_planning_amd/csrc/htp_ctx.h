@@ -92,6 +92,8 @@ struct htp_ctx {
   htp_event_pair envelope_ev;
   // tracking rollout (htp_track.hip)
   htp_event_pair track_ev;
+  // time-varying LQR (htp_lqr.hip)
+  htp_event_pair lqr_ev;
 };
 
 static inline int fail(htp_ctx* c, const std::string& m) {

@@ -281,6 +281,10 @@ class OBCAOptimizer(object):
         """Closed-loop tracking rollout of one solution dict (see track_batch)."""
         return track_batch([self], [solution], **opts)[0]
 
+    def lqr(self, solution: Dict, **opts) -> Dict:
+        """Time-varying LQR gains and error tube about one solution dict (see lqr_batch)."""
+        return lqr_batch([self], [solution], **opts)[0]
+
     # ------------------------------------------------------------- solve
     def solve(self, max_cpu_time=20, verbose: bool = False) -> Tuple[bool, Dict]:
         """optimizer.py:475-571.  max_cpu_time (IPOPT option, optimizer.py:486) limits
@@ -394,6 +398,26 @@ def track_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], device: 
     return [res.as_dict(k) for k in range(pk.batch)]
 
 
+def lqr_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], device: int = None, **opts) -> List[Dict]:
+    """Compute, on the device, the time-varying LQR about the trajectories of solution dicts (no counterpart in the
+    reference, which returns a trajectory and no controller for it): the NLP's own integrator linearised at every
+    stage, the gains K_i of the feedback law u = U_i - K_i (s - X_i) from a backward Riccati pass, the one-sigma tube
+    of the tracking error and of the feedback's control effort from a forward covariance pass, and the ratio of what
+    the acceleration, steering-rate, steering and speed limits leave beside the reference to that effort
+    (_native.Context.lqr; options: the weights, sigmas and k_sigma of _native.LQR_DEFAULTS, cost_to_go,
+    linearisation) -> one dict per solution: the metrics named in _native.LQR_METRICS, gains [N-1, 2, 5], the tube
+    columns, the worst stages and the flag names."""
+    if not optimizers:
+        return []
+    if len(optimizers) != len(solutions):
+        raise ValueError("[OBCA] lqr_batch needs one solution per optimizer")
+    dev = optimizers[0].device if device is None else device
+    pk = _native.PackedBatch([o.instance() for o in optimizers])
+    x = np.stack([o._decision_vector(s) for o, s in zip(optimizers, solutions)])
+    res = _context(dev).lqr(pk, x, **opts)
+    return [res.as_dict(k) for k in range(pk.batch)]
+
+
 def _repair_entries(optimizers, pk, res, aud, rep, out):
     for k, (o, (_, sol)) in enumerate(zip(optimizers, out)):
         if int(rep.state[k]) & _native.REPAIR_STATES["IMPROVED"]:
@@ -431,7 +455,7 @@ def repair_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], success
 
 def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: int = None, max_cpu_time=None,
                 audit: Dict = None, timeline: Dict = None, repair: Dict = None, envelope: Dict = None,
-                track: Dict = None):
+                track: Dict = None, lqr: Dict = None):
     """Solve many OBCAOptimizer problems in one HIP launch -> [(success, solution)].
     max_cpu_time (seconds, per problem, device clock; None/<= 0: no limit).  audit: options of audit_batch
     (a dict, possibly empty); when given, every solution dict gets an "audit" entry.  timeline: dict(dt=...);
@@ -440,7 +464,9 @@ def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: 
     the returned trajectory is the adopted one, and every solution dict gets a "repair" entry and the final
     "audit" entry (made with the repair's audit options).  envelope: options of envelope_batch (a dict, possibly
     empty); when given, every solution dict gets an "envelope" entry.  track: options of track_batch (a dict, possibly
-    empty); when given, every solution dict gets a "track" entry, of the repaired trajectory where a repair ran."""
+    empty); when given, every solution dict gets a "track" entry, of the repaired trajectory where a repair ran.
+    lqr: options of lqr_batch (a dict, possibly empty); when given, every solution dict gets an "lqr" entry, likewise
+    of the repaired trajectory."""
     if not optimizers:
         return []
     dev = optimizers[0].device if device is None else device
@@ -479,4 +505,8 @@ def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: 
         trk = ctx.track(pk, res.x, **track)
         for k, (_, sol) in enumerate(out):
             sol["track"] = trk.as_dict(k)
+    if lqr is not None:
+        lq = ctx.lqr(pk, res.x, **lqr)
+        for k, (_, sol) in enumerate(out):
+            sol["lqr"] = lq.as_dict(k)
     return out

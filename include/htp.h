@@ -552,6 +552,132 @@ int htp_obca_track_batch_device(htp_ctx* ctx, const htp_obca_batch* in, const do
 double htp_obca_track_last_ms(htp_ctx* ctx);
 
 /* ---------------------------------------------------------------------------
+ * Time-varying LQR gains and error tube of solved OBCA trajectories (no reference counterpart: the reference returns
+ * a trajectory and no controller for it).  For every problem of a batch: the NLP's own integrator linearised at
+ * every stage, the finite-horizon LQR gains K_i about the solved trajectory, the one-sigma tube of the tracking
+ * error and of the feedback's control effort under that law, and the authority the limits leave beside the
+ * reference.  Everything is a function of X, U and tau of x, six parameters and the options alone.
+ *   Read: X, U and tau of x; params DT, WHEELBASE (L), MAXSTEER, MAXV, MAXACC, MAXSR (as they stand, no absolute
+ *   value).  Polygons and duals are never read (the polygon arrays of `in` may be null).  sin, cos and tan are the
+ *   planner libm's; no product and sum are contracted.
+ *   State s = (x, y, v, theta, delta), control u = (a, w), f = the audit's kin =
+ *   (v cos theta, v sin theta, a, v tan delta / L, w); h_i = dT tau_i with time_opt, else dT; i = 0..N-2.
+ *   Jacobians.  Fx(s) has the entries (row, column)
+ *     (x, v) = cos theta          (x, theta) = -v sin theta
+ *     (y, v) = sin theta          (y, theta) = v cos theta
+ *     (theta, v) = tan delta / L  (theta, delta) = v / (L (cos delta)^2)
+ *   and zeros elsewhere; Fu has (v, a) = 1 and (delta, w) = 1.
+ *   Linearisation of the integrator about (X_i, U_i, h = h_i):
+ *     Euler (no time_opt):  A_i = I + h Fx(X_i),  B_i = h Fu.
+ *     Midpoint (time_opt):  m = X_i + (h / 2) f(X_i, U_i),  A_i = I + h Fx(m) (I + (h / 2) Fx(X_i)),
+ *                           B_i = h (Fu + (h / 2) Fx(m) Fu).
+ *   Products with the structural zeros and ones are not formed: rows v and delta of A_i are unit rows, columns x
+ *   and y unit columns, (theta, theta) is 1; B_i has (v, a) = (delta, w) = h, with time_opt also (x, a), (y, a),
+ *   (theta, a) and (theta, w), and zeros elsewhere.  With F = Fx(X_i), G = Fx(m) and hh = h / 2 the free entries are
+ *     A(r, v) = h (G(r, v) + G(r, theta) (hh F(theta, v))),  A(r, theta) = h G(r, theta),
+ *     A(r, delta) = h (G(r, theta) (hh F(theta, delta)))               for r = x, y;
+ *     A(theta, v) = h G(theta, v),  A(theta, delta) = h G(theta, delta);
+ *     B(r, a) = h (hh G(r, v)) for r = x, y, theta,  B(theta, w) = h (hh G(theta, delta)).
+ *   Weights (options, shared by the batch).  Q_i is diag(q_lon, q_lat, q_v, q_th, q_st) in the frame of node i, in
+ *   world coordinates with c = cos theta_i, s = sin theta_i:
+ *     Qxx = (c c) q_lon + (s s) q_lat,  Qxy = Qyx = (c s) (q_lon - q_lat),  Qyy = (s s) q_lon + (c c) q_lat,
+ *   the rest diagonal.  R = diag(r_a / MAXACC^2, r_w / MAXSR^2): the weights are on the controls normalised by the
+ *   problem's own limits, so one table suits a batch with different limits.
+ *   Backward pass.  P_{N-1} = qf Q_{N-1}.  For i = N-2 down to 0, with P = P_{i+1}, A = A_i, B = B_i:
+ *     T = P A,  S = R + B' (P B) (2 x 2),  K_i = S^-1 (B' T) by the closed-form inverse:
+ *       det = S00 S11 - S01 S10,  K(0, c) = (S11 g0 - S01 g1) / det,  K(1, c) = (S00 g1 - S10 g0) / det
+ *       with (g0, g1) = column c of B' T;
+ *     P_i = Q_i + T' (A - B K_i)   (= Q_i + A' P (A - B K_i): P is symmetric bit for bit),  then
+ *     P_i <- (P_i + P_i') / 2.
+ *   Every inner product is summed over k = 0..4 from left to right, the products with the structural zeros and
+ *   ones included; (B K)(r, c) = B(r, a) K(a, c) + B(r, w) K(w, c).
+ *   The feedback law is u = U_i - K_i (s - X_i); wrapping the theta difference of (s - X_i) is the caller's.
+ *   Forward pass.  Sigma_0 = diag(sig0_lon^2, sig0_lat^2, sig0_v^2, sig0_th^2, sig0_st^2) in the frame of X_0, in
+ *   world coordinates as Q.  With Acl = A_i - B_i K_i:
+ *     Sigma_{i+1} = (Acl Sigma_i) Acl' + h_i W_i,  then symmetrised as P;
+ *   W_i = diag(w_lon, w_lat, w_v, w_th, w_st) (variance per second) in the frame of node i, in world coordinates.
+ *   Tube row of node i, with c, s of theta_i and Sigma = Sigma_i:
+ *     var_lon = c (c Sxx + s Sxy) + s (c Syx + s Syy),  var_lat = s (s Sxx - c Sxy) - c (s Syx - c Syy),
+ *     var_v, var_theta, var_delta = the diagonal,  var_a, var_w = diag((K_i Sigma) K_i')  (0 at node N-1);
+ *     the row is the square roots (sigma_lon, sigma_lat, sigma_v, sigma_theta, sigma_delta, sigma_a, sigma_w); a
+ *     negative radicand is 0.
+ *   Authority.  Headroom: MAXACC - |a_i| and MAXSR - |w_i| at the stages i = 0..N-2, MAXSTEER - |delta_i| and
+ *   MAXV - |v_i| at the nodes i = 0..N-1.  ratio = headroom / sigma of the same quantity (sigma_a, sigma_w,
+ *   sigma_delta, sigma_v); +inf where sigma = 0 and headroom >= 0; negative where the reference itself is beyond
+ *   the limit.  The metrics carry each ratio's minimum over its stages.
+ *   Rejections: a non-finite double among those read -> NONFINITE; some h_i not > 0 -> BAD_TIME; a limit or the
+ *   wheelbase not > 0 -> BAD_LIMIT (both bits where both hold).  Then metrics are NaN, flags is those bits, and
+ *   nothing else is written.
+ *   SINGULAR.  Backward, at stage i: det not > 0, or a non-finite det, K_i or P_i entry.  Then the rows 0..i of
+ *   gains and of cost_to_go are NaN (the rows above keep their values), every tube row and every metric is NaN,
+ *   worst is -1; linearisation is complete.  Forward, at node i: a non-finite entry of the tube row or of
+ *   Sigma_{i+1}.  Then the tube rows i..N-1 and every metric are NaN and worst is -1.  No other flag is set.
+ *   The model is linear and the noise Gaussian and white; the clamps of the actuators are ignored, and the ratios
+ *   say where that assumption breaks.  The tube is evidence, not a bound.
+ *   One wavefront per problem, one launch.  The device equals a serial evaluation bit for bit: a stage's
+ *   linearisation is serial, every entry of every product is one serial sum, nothing is summed across lanes. */
+#define HTP_LQR_MAX_N HTP_AUDIT_MAX_N
+#define HTP_LQR_NTUBE 7              /* sigma_lon, sigma_lat, sigma_v, sigma_theta, sigma_delta, sigma_a, sigma_w */
+#define HTP_LQR_NGAIN 10             /* K_i row-major: 2 x 5 */
+#define HTP_LQR_NCTG 15              /* upper triangle of P_i, row-major */
+#define HTP_LQR_NLIN 35              /* A_i row-major (25), then B_i row-major (10) */
+enum {                               /* double metrics[batch][HTP_LQR_NMETRIC] */
+  HTP_LQR_MAX_SLAT = 0,              /* max sigma_lat over the nodes */
+  HTP_LQR_MAX_SLON,                  /* max sigma_lon */
+  HTP_LQR_MAX_STH,                   /* max sigma_theta */
+  HTP_LQR_END_SLAT,                  /* sigma_lat at node N-1 */
+  HTP_LQR_MAX_GAIN,                  /* max |K_i| entry over the stages */
+  HTP_LQR_TRACE_P0,                  /* trace P_0 */
+  HTP_LQR_RATIO_ACC,                 /* min (MAXACC - |a_i|) / sigma_a */
+  HTP_LQR_RATIO_RATE,                /* min (MAXSR - |w_i|) / sigma_w */
+  HTP_LQR_RATIO_STEER,               /* min (MAXSTEER - |delta_i|) / sigma_delta */
+  HTP_LQR_RATIO_SPEED,               /* min (MAXV - |v_i|) / sigma_v */
+  HTP_LQR_NMETRIC
+};
+enum {                               /* int32 flags[batch] */
+  HTP_LQR_AUTHORITY_ACC = 1,         /* HTP_LQR_RATIO_ACC < k_sigma */
+  HTP_LQR_AUTHORITY_RATE = 2,
+  HTP_LQR_AUTHORITY_STEER = 4,
+  HTP_LQR_AUTHORITY_SPEED = 8,
+  HTP_LQR_SINGULAR = 16,
+  HTP_LQR_NONFINITE = 32,
+  HTP_LQR_BAD_TIME = 64,
+  HTP_LQR_BAD_LIMIT = 128
+};
+typedef struct {
+  double q_lon, q_lat, q_v, q_th, q_st;            /* state weights, finite and >= 0 */
+  double qf;                                       /* terminal factor, finite and >= 0 */
+  double r_a, r_w;                                 /* control weights, finite and > 0 */
+  double sig0_lon, sig0_lat, sig0_v, sig0_th, sig0_st;   /* initial standard deviations, finite and >= 0 */
+  double w_lon, w_lat, w_v, w_th, w_st;            /* noise, variance per second, finite and >= 0 */
+  double k_sigma;                                  /* >= 0 (may be infinite) */
+} htp_obca_lqr_opts;
+typedef struct {
+  double* gains;            /* [batch][N-1][2][5] K_i */
+  double* tube;             /* [batch][N][HTP_LQR_NTUBE] */
+  double* metrics;          /* [batch][HTP_LQR_NMETRIC] */
+  int32_t* worst;           /* [batch][2] the node of HTP_LQR_MAX_SLAT and the stage of HTP_LQR_RATIO_RATE; ties go
+                               to the lowest */
+  int32_t* flags;           /* [batch] HTP_LQR_* bits */
+  double* cost_to_go;       /* nullable [batch][N][HTP_LQR_NCTG] */
+  double* linearisation;    /* nullable [batch][N-1][HTP_LQR_NLIN] */
+} htp_obca_lqr_result;
+/* API errors (-1 with an "[lqr]" message, nothing launched): a null required argument, N < 2 or > HTP_LQR_MAX_N,
+ * a negative or non-finite weight or sigma, r_a or r_w not > 0, k_sigma not >= 0, M, K or an edge count outside
+ * their ranges (3..8 for an edge count; they set the stride of x).  batch == 0 returns 0.  Nothing beyond the
+ * batch is ever written. */
+/* host pointers, synchronous; only [X | U | tau] of every x row is uploaded; what a flag leaves unwritten keeps the
+ * caller's values */
+int htp_obca_lqr_batch(htp_ctx* ctx, const htp_obca_batch* in, const double* x, const htp_obca_lqr_opts* opts,
+                       htp_obca_lqr_result* out);
+/* device pointers, enqueued on `stream`, not synchronised: behind htp_obca_solve_batch_device on the same stream it
+ * reads that solve's out->x without a host round trip */
+int htp_obca_lqr_batch_device(htp_ctx* ctx, const htp_obca_batch* in, const double* x, const htp_obca_lqr_opts* opts,
+                              htp_obca_lqr_result* out, void* stream);
+/* duration (ms) of the last lqr kernel (hipEvents on its stream) */
+double htp_obca_lqr_last_ms(htp_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * Warm start -> OBCA initial guess (R/obca_py/util.py get_init_ref_path :62-113
  * with cubic_spline.calc_spline_course :92-112): split at gear changes,
  * re-spline every segment over arc length at ds, v = gear * desired_v,
