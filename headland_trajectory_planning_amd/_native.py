@@ -482,6 +482,53 @@ class LqrResults:
         return d
 
 
+class LtrackOpts(ctypes.Structure):  # htp_obca_ltrack_opts
+    _fields_ = [("dt", ctypes.c_double), ("max_ticks", ctypes.c_int32), ("plant_substeps", ctypes.c_int32),
+                ("abort_dist", ctypes.c_double), ("margin_tol", ctypes.c_double), ("R", ctypes.c_int32),
+                ("scenarios", ctypes.c_void_p), ("gains", ctypes.c_void_p)]
+
+
+class LtrackResult(ctypes.Structure):  # htp_obca_ltrack_result
+    _fields_ = [(n, ctypes.c_void_p) for n in ("metrics", "worst", "flags", "tally", "worst_scenario",
+                                               "tick_clearance", "reference", "tick_error")]
+
+
+LTRACK_ERROR_COLUMNS = ("e_lat", "e_lon", "e_theta")
+
+
+def ltrack_opts(dt, max_ticks, scenarios_ptr, R, gains_ptr, plant_substeps=2, abort_dist=2.0, margin_tol=1e-4):
+    """htp_obca_ltrack_opts: track_opts without the three fixed gains, with the address of the LQR gains
+    [batch, N-1, 2, 5] (host or device, as the entry that takes it); the caller keeps both arrays alive."""
+    return LtrackOpts(float(dt), int(max_ticks), int(plant_substeps), float(abort_dist), float(margin_tol), int(R),
+                      scenarios_ptr, gains_ptr)
+
+
+class LtrackResults(TrackResults):
+    """TrackResults of a rollout under the LQR gains, plus tick_error [rows, max_ticks, 3] (LTRACK_ERROR_COLUMNS:
+    per pose the largest |e_lat|, |e_lon|, |e_theta| over the scenarios that reached it) or None, pre-filled with NaN
+    as the other per-tick arrays, and the gains [rows, N-1, 2, 5] the rollout ran under (None if they stayed on the
+    device)."""
+
+    def __init__(self, rows, R, max_ticks, scenarios=None, ticks=True, reference=False, errors=True, gains=None):
+        super().__init__(rows, R, max_ticks, scenarios, ticks, reference)
+        self.tick_error = np.full((rows, self.max_ticks, len(LTRACK_ERROR_COLUMNS)), np.nan) if errors else None
+        self.gains = gains
+
+    def struct(self):
+        r = LtrackResult()
+        for n in ("metrics", "worst", "flags", "tally", "worst_scenario"):
+            setattr(r, n, getattr(self, n).ctypes.data)
+        for n in ("tick_clearance", "reference", "tick_error"):
+            setattr(r, n, None if getattr(self, n) is None else getattr(self, n).ctypes.data)
+        return r
+
+    def as_dict(self, k):
+        d = super().as_dict(k)
+        if self.tick_error is not None:
+            d["tick_error"] = self.tick_error[k].copy()
+        return d
+
+
 class RepairOpts(ctypes.Structure):  # htp_obca_repair_opts
     _fields_ = [("rounds", ctypes.c_int32), ("pad", ctypes.c_double), ("max_raise", ctypes.c_double),
                 ("audit", AuditOpts)]
@@ -659,7 +706,8 @@ EXPORTS = ["htp_obca_sizes", "htp_create", "htp_destroy", "htp_last_error", "htp
            "htp_obca_repair_last_ms",
            "htp_obca_envelope_batch", "htp_obca_envelope_batch_device", "htp_obca_envelope_last_ms",
            "htp_obca_track_batch", "htp_obca_track_batch_device", "htp_obca_track_last_ms",
-           "htp_obca_lqr_batch", "htp_obca_lqr_batch_device", "htp_obca_lqr_last_ms"]
+           "htp_obca_lqr_batch", "htp_obca_lqr_batch_device", "htp_obca_lqr_last_ms",
+           "htp_obca_ltrack_batch", "htp_obca_ltrack_batch_device", "htp_obca_ltrack_last_ms"]
 
 
 def _declare(lib):
@@ -815,6 +863,14 @@ def _declare(lib):
         lib.htp_obca_lqr_batch_device.restype = ctypes.c_int
         lib.htp_obca_lqr_last_ms.argtypes = [ctypes.c_void_p]
         lib.htp_obca_lqr_last_ms.restype = ctypes.c_double
+    if hasattr(lib, "htp_obca_ltrack_batch"):   # likewise
+        lib.htp_obca_ltrack_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(ObcaBatch), ctypes.c_void_p,
+                                              ctypes.POINTER(LtrackOpts), ctypes.POINTER(LtrackResult)]
+        lib.htp_obca_ltrack_batch.restype = ctypes.c_int
+        lib.htp_obca_ltrack_batch_device.argtypes = lib.htp_obca_ltrack_batch.argtypes + [ctypes.c_void_p]
+        lib.htp_obca_ltrack_batch_device.restype = ctypes.c_int
+        lib.htp_obca_ltrack_last_ms.argtypes = [ctypes.c_void_p]
+        lib.htp_obca_ltrack_last_ms.restype = ctypes.c_double
     if hasattr(lib, "htp_mfma_f64_probe"):   # absent from libraries built before it (A/B variants of old kernels)
         lib.htp_mfma_f64_probe.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
         lib.htp_mfma_f64_probe.restype = ctypes.c_int
@@ -1849,6 +1905,60 @@ class Context:
 
     def lqr_last_ms(self):
         return self.lib.htp_obca_lqr_last_ms(self.ctx)
+
+    def ltrack(self, packed, x, gains=None, scenarios=None, dt=0.1, max_ticks=None, ticks=True, reference=False,
+               errors=True, R=64, seed=0, plant_substeps=2, abort_dist=2.0, margin_tol=1e-4, **lqr_opts_):
+        """Closed-loop rollout of decision vectors x [batch, n_var] of `packed` under their time-varying LQR gains and
+        every scenario (host buffers) -> LtrackResults.  gains [batch, N-1, 2, 5] (LqrResults.gains); None runs
+        lqr(packed, x, **lqr_opts_) first.  scenarios, dt, max_ticks, ticks, reference, R, seed as track's; errors
+        asks for tick_error."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (packed.batch, packed.n_var):
+            raise ValueError(f"[htp] ltrack: x must be [{packed.batch}, {packed.n_var}], got {x.shape}")
+        if gains is None:
+            gains = self.lqr(packed, x, **lqr_opts_).gains
+        elif lqr_opts_:
+            raise TypeError(f"[htp] ltrack: unknown options {sorted(lqr_opts_)} (LQR options need gains=None)")
+        gains = np.ascontiguousarray(gains, dtype=np.float64)
+        if gains.shape != (packed.batch, packed.N - 1, 2, 5):
+            raise ValueError(f"[htp] ltrack: gains must be [{packed.batch}, {packed.N - 1}, 2, 5], got {gains.shape}")
+        if scenarios is None:
+            scenarios = track_scenarios(R, seed)
+        scenarios = np.ascontiguousarray(scenarios, dtype=np.float64)
+        if scenarios.ndim != 2 or scenarios.shape[1] != len(TRACK_SCENARIO_COLUMNS):
+            raise ValueError(f"[htp] ltrack: scenarios must be [R, 6], got {scenarios.shape}")
+        if max_ticks is None:
+            if not (np.isfinite(dt) and dt > 0):
+                raise ValueError(f"[htp] ltrack: dt must be finite and > 0, got {dt}")
+            max_ticks = track_ticks(packed, x, dt)
+        res = LtrackResults(packed.batch, scenarios.shape[0], max(int(max_ticks), 0), scenarios, ticks, reference,
+                            errors, gains)
+        b, r = packed.struct(), res.struct()
+        o = ltrack_opts(dt, max_ticks, scenarios.ctypes.data, scenarios.shape[0], gains.ctypes.data, plant_substeps,
+                        abort_dist, margin_tol)
+        rc = self.lib.htp_obca_ltrack_batch(self.ctx, ctypes.byref(b), x.ctypes.data, ctypes.byref(o), ctypes.byref(r))
+        if rc != 0:
+            raise RuntimeError(f"[htp] htp_obca_ltrack_batch failed: {self.error()}")
+        return res
+
+    def ltrack_device(self, packed, dev_ptrs, x_ptr, gains_ptr, scenarios_ptr, R, out_ptrs, dt, max_ticks, stream=None,
+                      lo=None, hi=None, **opts):
+        """Device-resident rollout under the LQR gains of `packed` (or of its problems [lo, hi)) on `stream`, not
+        synchronised.  x_ptr: device pointer of the [batch, n_var] rows (e.g. a solve's out x); gains_ptr: device
+        [batch, N-1, 2, 5] (e.g. what lqr_device wrote on the same stream); scenarios_ptr: device [R, 6]; out_ptrs:
+        those of track_device and optionally tick_error [batch, max_ticks, 3]."""
+        b = packed.struct(dev_ptrs) if lo is None else packed.chunk_struct(dev_ptrs, lo, hi)
+        r = LtrackResult()
+        for k, v in out_ptrs.items():
+            setattr(r, k, v)
+        o = ltrack_opts(dt, max_ticks, scenarios_ptr, R, gains_ptr, **opts)
+        rc = self.lib.htp_obca_ltrack_batch_device(self.ctx, ctypes.byref(b), x_ptr, ctypes.byref(o), ctypes.byref(r),
+                                                   stream)
+        if rc != 0:
+            raise RuntimeError(f"[htp] htp_obca_ltrack_batch_device failed: {self.error()}")
+
+    def ltrack_last_ms(self):
+        return self.lib.htp_obca_ltrack_last_ms(self.ctx)
 
     def _repair_call(self, name, *args):
         if getattr(self.lib, name)(self.ctx, *args) != 0:

@@ -94,6 +94,8 @@ struct htp_ctx {
   htp_event_pair track_ev;
   // time-varying LQR (htp_lqr.hip)
   htp_event_pair lqr_ev;
+  // rollout under the LQR gains (htp_ltrack.hip)
+  htp_event_pair ltrack_ev;
 };
 
 static inline int fail(htp_ctx* c, const std::string& m) {

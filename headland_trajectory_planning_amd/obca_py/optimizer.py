@@ -285,6 +285,10 @@ class OBCAOptimizer(object):
         """Time-varying LQR gains and error tube about one solution dict (see lqr_batch)."""
         return lqr_batch([self], [solution], **opts)[0]
 
+    def ltrack(self, solution: Dict, **opts) -> Dict:
+        """Closed-loop rollout of one solution dict under its LQR gains (see ltrack_batch)."""
+        return ltrack_batch([self], [solution], **opts)[0]
+
     # ------------------------------------------------------------- solve
     def solve(self, max_cpu_time=20, verbose: bool = False) -> Tuple[bool, Dict]:
         """optimizer.py:475-571.  max_cpu_time (IPOPT option, optimizer.py:486) limits
@@ -418,6 +422,24 @@ def lqr_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], device: in
     return [res.as_dict(k) for k in range(pk.batch)]
 
 
+def ltrack_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], device: int = None, **opts) -> List[Dict]:
+    """Drive, on the device, the kinematic plant of track_batch along the trajectories of solution dicts under the
+    time-varying LQR law u = u_ff - K_i e of lqr_batch instead of the fixed three-gain controller, with the same
+    scenario table, limits and clearance measurement (_native.Context.ltrack; options gains [batch, N-1, 2, 5] or the
+    LQR's own options to compute them, scenarios or R and seed, dt, max_ticks, plant_substeps, abort_dist,
+    margin_tol, ticks, reference, errors) -> one dict per solution: the entries of track_batch plus tick_error
+    [max_ticks, 3], per pose the largest |e_lat|, |e_lon|, |e_theta| over the scenarios."""
+    if not optimizers:
+        return []
+    if len(optimizers) != len(solutions):
+        raise ValueError("[OBCA] ltrack_batch needs one solution per optimizer")
+    dev = optimizers[0].device if device is None else device
+    pk = _native.PackedBatch([o.instance() for o in optimizers])
+    x = np.stack([o._decision_vector(s) for o, s in zip(optimizers, solutions)])
+    res = _context(dev).ltrack(pk, x, **opts)
+    return [res.as_dict(k) for k in range(pk.batch)]
+
+
 def _repair_entries(optimizers, pk, res, aud, rep, out):
     for k, (o, (_, sol)) in enumerate(zip(optimizers, out)):
         if int(rep.state[k]) & _native.REPAIR_STATES["IMPROVED"]:
@@ -455,7 +477,7 @@ def repair_batch(optimizers: List[OBCAOptimizer], solutions: List[Dict], success
 
 def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: int = None, max_cpu_time=None,
                 audit: Dict = None, timeline: Dict = None, repair: Dict = None, envelope: Dict = None,
-                track: Dict = None, lqr: Dict = None):
+                track: Dict = None, lqr: Dict = None, ltrack: Dict = None):
     """Solve many OBCAOptimizer problems in one HIP launch -> [(success, solution)].
     max_cpu_time (seconds, per problem, device clock; None/<= 0: no limit).  audit: options of audit_batch
     (a dict, possibly empty); when given, every solution dict gets an "audit" entry.  timeline: dict(dt=...);
@@ -466,7 +488,9 @@ def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: 
     empty); when given, every solution dict gets an "envelope" entry.  track: options of track_batch (a dict, possibly
     empty); when given, every solution dict gets a "track" entry, of the repaired trajectory where a repair ran.
     lqr: options of lqr_batch (a dict, possibly empty); when given, every solution dict gets an "lqr" entry, likewise
-    of the repaired trajectory."""
+    of the repaired trajectory.  ltrack: options of ltrack_batch (a dict, possibly empty); when given, every solution
+    dict gets an "ltrack" entry: the rollout under the gains of the "lqr" entry where lqr was asked for too, else
+    under gains computed with the LQR options inside ltrack."""
     if not optimizers:
         return []
     dev = optimizers[0].device if device is None else device
@@ -509,4 +533,8 @@ def solve_batch(optimizers: List[OBCAOptimizer], verbose: bool = False, device: 
         lq = ctx.lqr(pk, res.x, **lqr)
         for k, (_, sol) in enumerate(out):
             sol["lqr"] = lq.as_dict(k)
+    if ltrack is not None:
+        ltk = ctx.ltrack(pk, res.x, **({**ltrack, "gains": lq.gains} if lqr is not None else ltrack))
+        for k, (_, sol) in enumerate(out):
+            sol["ltrack"] = ltk.as_dict(k)
     return out

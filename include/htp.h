@@ -678,6 +678,77 @@ int htp_obca_lqr_batch_device(htp_ctx* ctx, const htp_obca_batch* in, const doub
 double htp_obca_lqr_last_ms(htp_ctx* ctx);
 
 /* ---------------------------------------------------------------------------
+ * Closed-loop rollout of solved OBCA trajectories under their time-varying LQR gains (no reference counterpart).
+ * The tracking rollout above with one change: the fixed three-gain controller is replaced by the law
+ * u = u_ff - K_i e of the LQR section, with the gains K_i handed in (htp_obca_lqr_result.gains of the same x).
+ *   Exactly as the tracking rollout's text above, word for word: what is read (plus the gains); node times, n, np and
+ *   TRUNCATED; ref(k); the problem-level rejections; the scenario row and the initial state; the errors, the
+ *   clearance and the maxima at pose k; DIVERGED; the plant; BAD_POLYTOPE; the tally; the worst scenario.  The eight
+ *   metrics and the ten flag bits are HTP_TRACK_*.
+ *   Gains.  All 10 (N - 1) gains of a problem count as read: a non-finite one is the problem-level NONFINITE
+ *   rejection (so a problem the LQR left SINGULAR, whose gain rows are NaN, is rejected).
+ *   Control for tick k -> k + 1 (only while k + 1 < np).  i = the largest index in 0..N-2 with t_i <= fl(k dt) (the
+ *   interval rule of ref(k), applied for k >= n too), (ci, si) = sincos(X_i.theta), K = K_i (2 x 5, rows a and w,
+ *   columns x, y, v, theta, delta).  For r = 0 (a) and r = 1 (w):
+ *     k_lon(r) = ci K(r,0) + si K(r,1),   k_lat(r) = ci K(r,1) - si K(r,0)
+ *   i.e. the position gains rotated into the frame of node i; they are applied to the errors taken in the frame of
+ *   ref(k): with ref(k) = X_i this is K_i (s - X_i) algebraically, inside a stage the law follows the heading of the
+ *   reference.  With (xr, yr, vr, thr, dr) = ref(k), e_lon, e_lat and e_th those of pose k (the wrapped atan2 is
+ *   the wrapping the LQR text leaves to the caller), e_v = v - vr and e_d = delta - dr:
+ *     fb(r) = (((k_lon(r) e_lon + k_lat(r) e_lat) + K(r,2) e_v) + K(r,3) e_th) + K(r,4) e_d
+ *   Feedforward, r+ = ref(k + 1):  a_ff = (vr+ - vr) / dt,  w_ff = (dr+ - dr) / dt.  Both of the NLP's integrators
+ *   are linear in a and w for v and delta, so this is the tick's mean control even where the tick straddles a stage
+ *   boundary (holding U_i would not be).
+ *     a_cmd = a_ff - fb(0),   w_cmd = w_ff - fb(1)
+ *     v_des = clamp(v + dt a_cmd, +-MAXV)                    (a set-point limit: it sets no flag)
+ *     a     = clamp((v_des - v) / dt, +-MAXACC)               bites -> SAT_ACC
+ *     d_des = clamp(delta + dt w_cmd, +-MAXSTEER)             bites -> SAT_STEER
+ *     w     = clamp((d_des - delta) / dt, +-MAXSR)            bites -> SAT_RATE
+ *   SAT_SHARE counts ticks as the tracking rollout does.
+ *   tick_error[k] = the maxima over the scenarios that reached pose k of (|e_lat|, |e_lon|, |e_th|), in that order;
+ *   0 where none did; an error that is NaN counts as 0.  A maximum does not depend on the order it is taken in.  It
+ *   is not written for a rejected problem, nor at or beyond np.
+ *   What it does not promise.  K_i was designed for the step h_i and is applied at the period dt; the clamps are
+ *   outside the design; the plant's slip, bias and yaw gain are outside the LQR's noise model.  Whether the law
+ *   helps is a question to measure (tools/ltrack_outcomes.py), not a property of this entry.
+ *   One wavefront per problem, one lane per scenario, one launch; the device equals a serial evaluation bit for
+ *   bit, as the tracking rollout does. */
+typedef struct {
+  double dt;                         /* control period, finite and > 0 */
+  int32_t max_ticks;                 /* poses of storage per problem, >= 2 */
+  int32_t plant_substeps;            /* 1 .. HTP_TRACK_MAX_SUBSTEPS */
+  double abort_dist;                 /* > 0 (may be infinite) */
+  double margin_tol;                 /* finite and >= 0 */
+  int32_t R;                         /* scenarios, 1 .. HTP_TRACK_MAX_SCENARIOS */
+  const double* scenarios;           /* [R][HTP_TRACK_NDIST], shared by the batch */
+  const double* gains;               /* [batch][N-1][2][5], the layout of htp_obca_lqr_result.gains */
+} htp_obca_ltrack_opts;
+typedef struct {
+  double* metrics;          /* [batch][R][HTP_TRACK_NMETRIC] */
+  int32_t* worst;           /* [batch][R][3] */
+  int32_t* flags;           /* [batch][R] HTP_TRACK_* bits */
+  int32_t* tally;           /* [batch][HTP_TRACK_NFLAG] */
+  int32_t* worst_scenario;  /* [batch] */
+  double* tick_clearance;   /* nullable [batch][max_ticks] */
+  double* reference;        /* nullable [batch][max_ticks][HTP_TRACK_NREF] */
+  double* tick_error;       /* nullable [batch][max_ticks][3]: max |e_lat|, |e_lon|, |e_th| per pose; entries at or
+                               beyond np are never written */
+} htp_obca_ltrack_result;
+/* API errors (-1 with an "[ltrack]" message, nothing launched): those of the tracking rollout less its gain checks,
+ * and a null gains.  batch == 0 returns 0.  Nothing beyond the batch is ever written. */
+/* host pointers (scenarios and gains too), synchronous; the entries of the three per-tick outputs that are never
+ * written keep the caller's values */
+int htp_obca_ltrack_batch(htp_ctx* ctx, const htp_obca_batch* in, const double* x, const htp_obca_ltrack_opts* opts,
+                          htp_obca_ltrack_result* out);
+/* device pointers (scenarios and gains too), enqueued on `stream`, not synchronised: behind
+ * htp_obca_solve_batch_device and htp_obca_lqr_batch_device on the same stream it rolls that solve's out->x under
+ * that pass's out->gains without a host round trip */
+int htp_obca_ltrack_batch_device(htp_ctx* ctx, const htp_obca_batch* in, const double* x,
+                                 const htp_obca_ltrack_opts* opts, htp_obca_ltrack_result* out, void* stream);
+/* duration (ms) of the last ltrack kernel (hipEvents on its stream) */
+double htp_obca_ltrack_last_ms(htp_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * Warm start -> OBCA initial guess (R/obca_py/util.py get_init_ref_path :62-113
  * with cubic_spline.calc_spline_course :92-112): split at gear changes,
  * re-spline every segment over arc length at ds, v = gear * desired_v,
