@@ -707,7 +707,8 @@ EXPORTS = ["htp_obca_sizes", "htp_create", "htp_destroy", "htp_last_error", "htp
            "htp_obca_envelope_batch", "htp_obca_envelope_batch_device", "htp_obca_envelope_last_ms",
            "htp_obca_track_batch", "htp_obca_track_batch_device", "htp_obca_track_last_ms",
            "htp_obca_lqr_batch", "htp_obca_lqr_batch_device", "htp_obca_lqr_last_ms",
-           "htp_obca_ltrack_batch", "htp_obca_ltrack_batch_device", "htp_obca_ltrack_last_ms"]
+           "htp_obca_ltrack_batch", "htp_obca_ltrack_batch_device", "htp_obca_ltrack_last_ms",
+           "htp_classic_sample_batch", "htp_classic_sample_batch_device", "htp_classic_sample_last_ms"]
 
 
 def _declare(lib):
@@ -874,6 +875,13 @@ def _declare(lib):
     if hasattr(lib, "htp_mfma_f64_probe"):   # absent from libraries built before it (A/B variants of old kernels)
         lib.htp_mfma_f64_probe.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p]
         lib.htp_mfma_f64_probe.restype = ctypes.c_int
+    lib.htp_classic_sample_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(SmpIn), ctypes.POINTER(SmpResult)]
+    lib.htp_classic_sample_batch.restype = ctypes.c_int
+    lib.htp_classic_sample_batch_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(SmpIn), ctypes.POINTER(SmpResult),
+                                                    ctypes.c_void_p]
+    lib.htp_classic_sample_batch_device.restype = ctypes.c_int
+    lib.htp_classic_sample_last_ms.argtypes = [ctypes.c_void_p]
+    lib.htp_classic_sample_last_ms.restype = ctypes.c_double
     if hasattr(lib, "htp_bk_probe"):   # likewise
         lib.htp_bk_probe.argtypes = [ctypes.c_void_p] + BK_PROBE_ARGS + [ctypes.c_void_p]
         lib.htp_bk_probe.restype = ctypes.c_int
@@ -1532,6 +1540,123 @@ class ClassicResults:
         return self.path[b, :int(self.n_path[b])].copy()
 
 
+# ------------------------------------------------------------ sampled exit / entry pose search (htp_sample.hip)
+SMP_NDESC, SMP_NPOSE = 6, 8
+SMP_MAX_POLY, SMP_MAX_VERT = 48, 256
+SMP_TYPES = {"dubins": 0, "reeds_shepp": 1, "circle_back": 2}
+SMP_OK, SMP_NONE_FEASIBLE, SMP_OVERFLOW, SMP_BAD_INPUT = 0, 1, 2, 3
+SMP_STATUS = {0: "ok", 1: "none_feasible", 2: "overflow", 3: "bad_input"}
+SMP_C_FEASIBLE, SMP_C_BLOCKED, SMP_C_PLANNER, SMP_C_OVERFLOW, SMP_C_BAD_INPUT, SMP_C_UNUSED = range(6)
+SMP_C_STATUS = {0: "feasible", 1: "blocked", 2: "planner", 3: "overflow", 4: "bad_input", 5: "unused"}
+
+
+class SmpIn(ctypes.Structure):  # htp_classic_sample_in
+    _fields_ = [("batch", ctypes.c_int32), ("npoly", ctypes.c_int32), ("nvert", ctypes.c_int32),
+                ("params", ctypes.c_void_p), ("desc", ctypes.c_void_p), ("poly_off", ctypes.c_void_p),
+                ("vertices", ctypes.c_void_p), ("start_x", ctypes.c_void_p), ("end_x", ctypes.c_void_p),
+                ("n_start", ctypes.c_void_p), ("n_end", ctypes.c_void_p), ("cap_s", ctypes.c_int32),
+                ("cap_e", ctypes.c_int32), ("cap_cand", ctypes.c_int32), ("cap_samples", ctypes.c_int32),
+                ("max_groups", ctypes.c_int32)]
+
+
+class SmpResult(ctypes.Structure):  # htp_classic_sample_result
+    _fields_ = [("status", ctypes.c_void_p), ("winner", ctypes.c_void_p), ("poses", ctypes.c_void_p),
+                ("score", ctypes.c_void_p), ("n_feasible", ctypes.c_void_p), ("cand_score", ctypes.c_void_p),
+                ("cand_status", ctypes.c_void_p)]
+
+
+class SamplePacked:
+    """Turns for htp_classic_sample_batch.  A turn is a dict (path_planner.safety_forward_path_plan.sample_turn builds
+    it): type ("dubins" / "reeds_shepp" / "circle_back"), side (map_utils NEAR_SIDE 1 / FAR_SIDE 2), start, end (the
+    base poses x, y, yaw), start_x, end_x (the candidate lists), wheel_base, max_steer, radius, step, body (car_poly
+    ring), aux (0-2 implement rings), blockers (obs_poly_list rings), field (the field ring).  Turns that share the
+    very same polygon arrays (`is`) share their pool entries.  cap_s / cap_e / cap_cand default to the largest list
+    and product of the batch; max_groups = 0 lets the library choose the candidate kernel's workgroup count."""
+
+    def __init__(self, turns, cap_s=None, cap_e=None, cap_cand=None, cap_samples=1024, max_groups=0):
+        B = len(turns)
+        self.batch, self.cap_samples, self.max_groups = B, int(cap_samples), int(max_groups)
+        sx = [np.asarray(t["start_x"], dtype=np.float64).reshape(-1) for t in turns]
+        ex = [np.asarray(t["end_x"], dtype=np.float64).reshape(-1) for t in turns]
+        self.cap_s = int(cap_s) if cap_s is not None else max([len(v) for v in sx] + [1])
+        self.cap_e = int(cap_e) if cap_e is not None else max([len(v) for v in ex] + [1])
+        self.cap_cand = int(cap_cand) if cap_cand is not None else max([len(a) * len(b) for a, b in zip(sx, ex)] + [1])
+        self.params = np.zeros((B, CT_NPARAM))
+        self.desc = np.full((B, SMP_NDESC), -1, np.int32)
+        self.start_x = np.zeros((B, self.cap_s))
+        self.end_x = np.zeros((B, self.cap_e))
+        self.n_start = np.array([len(v) for v in sx], np.int32).reshape(B)
+        self.n_end = np.array([len(v) for v in ex], np.int32).reshape(B)
+        polys, seen = [], {}
+
+        def add(q):
+            if id(q) in seen:
+                return seen[id(q)]
+            polys.append(np.asarray(q, dtype=np.float64).reshape(-1, 2))
+            seen[id(q)] = len(polys) - 1
+            return len(polys) - 1
+        self._keep = []   # the rings `seen` knows by id stay alive while packing
+        for b, t in enumerate(turns):
+            self.params[b] = [SMP_TYPES[t["type"]], t.get("side", 1), *np.asarray(t["start"], dtype=np.float64)[:3],
+                              *np.asarray(t["end"], dtype=np.float64)[:3], t["wheel_base"], t["max_steer"],
+                              t["radius"], t.get("step", 0.1)]
+            self.start_x[b, :min(len(sx[b]), self.cap_s)] = sx[b][:self.cap_s]
+            self.end_x[b, :min(len(ex[b]), self.cap_e)] = ex[b][:self.cap_e]
+            aux = list(t.get("aux", []))
+            if len(aux) > 2:
+                raise ValueError("[htp] sample: at most two implements")
+            self._keep += [t["body"], t["field"]] + aux
+            self.desc[b, 0] = add(t["body"])
+            for a, q in enumerate(aux):
+                self.desc[b, 1 + a] = add(q)
+            blk = t.get("blockers", [])
+            key = id(blk)
+            if key in seen:
+                self.desc[b, 3], self.desc[b, 4] = seen[key]
+            else:
+                b0 = len(polys)
+                polys += [np.asarray(q, dtype=np.float64).reshape(-1, 2) for q in blk]
+                seen[key] = (b0, len(polys))
+                self._keep.append(blk)
+                self.desc[b, 3], self.desc[b, 4] = b0, len(polys)
+            self.desc[b, 5] = add(t["field"])
+        self.poly_off = np.concatenate([[0], np.cumsum([len(q) for q in polys])]).astype(np.int32)
+        self.vertices = np.ascontiguousarray(np.concatenate(polys) if polys else np.zeros((0, 2)))
+
+    def struct(self, ptrs=None):
+        p = ptrs or {}
+
+        def g(name):
+            return p.get(name, getattr(self, name).ctypes.data)
+        return SmpIn(self.batch, len(self.poly_off) - 1, self.vertices.shape[0], g("params"), g("desc"), g("poly_off"),
+                     g("vertices"), g("start_x"), g("end_x"), g("n_start"), g("n_end"), self.cap_s, self.cap_e,
+                     self.cap_cand, self.cap_samples, self.max_groups)
+
+
+class SampleResults:
+    """status [B] (SMP_*), winner [B, 2], poses [B, 8] (safe start, safe end, leave_offset, enter_offset), score [B],
+    n_feasible [B]; with tables=True cand_score / cand_status [B, cap_cand] (-inf / SMP_C_*)."""
+
+    def __init__(self, packed, tables=True):
+        B = packed.batch
+        self.status = np.zeros(B, np.int32)
+        self.winner = np.zeros((B, 2), np.int32)
+        self.poses = np.zeros((B, SMP_NPOSE))
+        self.score = np.zeros(B)
+        self.n_feasible = np.zeros(B, np.int32)
+        self.cand_score = np.zeros((B, packed.cap_cand)) if tables else None
+        self.cand_status = np.zeros((B, packed.cap_cand), np.int32) if tables else None
+
+    def struct(self, ptrs=None):
+        p = ptrs or {}
+
+        def g(name):
+            a = getattr(self, name)
+            return p.get(name, None if a is None else a.ctypes.data)
+        return SmpResult(g("status"), g("winner"), g("poses"), g("score"), g("n_feasible"), g("cand_score"),
+                         g("cand_status"))
+
+
 class ChainBatch(ctypes.Structure):  # htp_chain_batch
     _fields_ = [("batch", ctypes.c_int32), ("N", ctypes.c_int32), ("M", ctypes.c_int32),
                 ("scenes", OgeBatch), ("turns", CtBatch), ("margin", ctypes.c_void_p),
@@ -1682,6 +1807,33 @@ class Context:
 
     def classic_last_ms(self):
         return self.lib.htp_classic_last_ms(self.ctx)
+
+    def classic_sample(self, packed, tables=True, **opts):
+        """Batched sampled exit / entry pose search (host buffers) -> SampleResults.  opts: max_groups (workgroups of
+        the candidate kernel, 0 = the library's choice) and cap_samples override the packed values."""
+        for k in opts:
+            if k not in ("max_groups", "cap_samples"):
+                raise TypeError(f"[htp] classic_sample: unknown option {k!r}")
+        rs = SampleResults(packed, tables)
+        b, r = packed.struct(), rs.struct()
+        b.max_groups = int(opts.get("max_groups", packed.max_groups))
+        b.cap_samples = int(opts.get("cap_samples", packed.cap_samples))
+        if self.lib.htp_classic_sample_batch(self.ctx, ctypes.byref(b), ctypes.byref(r)) != 0:
+            raise RuntimeError(f"[htp] htp_classic_sample_batch failed: {self.error()}")
+        return rs
+
+    def classic_sample_device(self, packed, dev_ptrs, out_ptrs, stream=None, **opts):
+        """Device-resident search on `stream`, not synchronised.  dev_ptrs: device pointers of the SamplePacked arrays
+        by name; out_ptrs: those of the SampleResults arrays (cand_score / cand_status optional, as a pair)."""
+        b, r = packed.struct(dev_ptrs), SmpResult()
+        b.max_groups = int(opts.get("max_groups", packed.max_groups))
+        for k, v in out_ptrs.items():
+            setattr(r, k, v)
+        if self.lib.htp_classic_sample_batch_device(self.ctx, ctypes.byref(b), ctypes.byref(r), stream) != 0:
+            raise RuntimeError(f"[htp] htp_classic_sample_batch_device failed: {self.error()}")
+
+    def classic_sample_last_ms(self):
+        return self.lib.htp_classic_sample_last_ms(self.ctx)
 
     def oge_obstacles(self, packed, halfspaces=True):
         """Batched orchard scene -> OBCA obstacle polygons (+ halfspaces), host buffers -> OgeResults."""

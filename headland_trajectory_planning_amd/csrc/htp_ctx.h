@@ -96,6 +96,10 @@ struct htp_ctx {
   htp_event_pair lqr_ev;
   // rollout under the LQR gains (htp_ltrack.hip)
   htp_event_pair ltrack_ev;
+  // sampled pose search (htp_sample.hip): per-workgroup planner scratch, candidate tables when the caller has none
+  htp_event_pair sample_ev;
+  htp_device_buffer sample_ws, sample_tab;
+  int sample_groups = 0;   // workgroups of the candidate kernel resident at once (0: not yet asked)
 };
 
 static inline int fail(htp_ctx* c, const std::string& m) {

@@ -185,6 +185,29 @@ def simple_contains(field, F):
     return ok & inside.all(1)
 
 
+def ring_signed_distance(ring, P):
+    """Signed distance of the points P (..., 2) to the simple ring (m, 2): Euclidean distance to the nearest ring
+    segment, positive inside (the crossing-number rule of simple_contains), negative outside."""
+    P = np.asarray(P, dtype=np.float64)
+    X, Y = P[..., 0], P[..., 1]
+    V = ring.shape[0]
+    inside = np.zeros(X.shape, dtype=bool)
+    d2 = np.full(X.shape, np.inf)
+    for i in range(V):
+        (xi, yi), (xj, yj) = ring[i], ring[(i + 1) % V]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            xc = (xj - xi) * (Y - yi) / (yj - yi) + xi
+        inside ^= ((yi > Y) != (yj > Y)) & (X < xc)
+        ex, ey = xj - xi, yj - yi
+        ee = ex * ex + ey * ey
+        t = ((X - xi) * ex + (Y - yi) * ey) / ee if ee > 0.0 else np.zeros(X.shape)
+        t = np.clip(t, 0.0, 1.0)
+        px, py = (xi + t * ex) - X, (yi + t * ey) - Y
+        d2 = np.minimum(d2, px * px + py * py)
+    d = np.sqrt(d2)
+    return np.where(inside, d, -d)
+
+
 def union_contains(lanes, F):
     """Footprints F[p] inside the union of the convex rings `lanes` (edge coverage)."""
     A = F.reshape(-1, 2)

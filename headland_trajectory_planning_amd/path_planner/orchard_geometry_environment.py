@@ -13,7 +13,8 @@ import math
 
 import numpy as np
 
-from .geom import Polygon, buffer_point_square, buffer_segment_flat, convex_intersects, ring_of, simple_contains
+from .geom import (Polygon, buffer_point_square, buffer_segment_flat, convex_intersects, ring_of, ring_signed_distance,
+                   simple_contains)
 
 
 class OrchardGeometryEnvironment(object):
@@ -148,6 +149,22 @@ class OrchardGeometryEnvironment(object):
 
     def create_obstacle_polygons(self, obstacles, obstacle_dim):
         return [buffer_point_square(float(o[0]), float(o[1]), obstacle_dim) for o in obstacles]
+
+    def get_min_distance_to_boundary(self, car_model, path, with_aux=True):
+        """:393-412: the least signed distance to the field ring (positive inside, negative outside) over the swept
+        footprint's points.  The reference walks exterior.coords of the shapely union of the placed polygons; this
+        takes every corner of every placed polygon (the body at every pose, each implement at every second pose).
+        For a convex field ring the two minima are the same number; for a non-convex one (l_std > 0) they can
+        differ -- DESIGN.md s.3.16 states the deviation."""
+        path = np.asarray(path, dtype=np.float64)
+        path = path.reshape(-1, path.shape[-1])[:, :3]
+        body, aux = car_model.get_path_poly(path)
+        field = ring_of(self.field_range_poly)
+        min_distance = np.inf
+        for F in [body] + (list(aux) if with_aux else []):
+            if F.size:
+                min_distance = min(min_distance, float(ring_signed_distance(field, F).min()))
+        return min_distance
 
     def check_path_feasibility(self, car_model, path, boundary_check=True, aux_check=False):
         """:423-458 (nearest-then-intersects == any intersects)."""

@@ -225,3 +225,212 @@ def classic_circle_back_turning_path(start_exit_pose, end_enter_pose, map_env, c
         enter = get_dubins_path_full(turning_path[-1, :3], end_enter_pose, radius)
         turning_path = np.vstack([turning_path, enter])
     return turning_path
+
+
+# ---------------------------------------------------------------- sampled exit / entry poses (:457-790)
+# The three sample_start_end_pose_for_* functions below are the reference's loops evaluated on the host, like the
+# planners above; sample_start_end_pose_batch runs the same search for many turns in one launch of
+# htp_classic_sample_batch (csrc/sample_core.h).
+def _sample_x_lists(map_tree_rows, start_row_id, end_row_id, car, side, accuracy, extra_offset_enter_dist,
+                    extra_offset_leave_dist):
+    """:470-519 / :571-620: the base poses and the np.arange lists of exit / entry x values."""
+    start_base = get_base_pose(start_row_id, map_tree_rows, min_offset=extra_offset_leave_dist, side=side,
+                               pose_type=LEAVE_POSE)
+    end_base = get_base_pose(end_row_id, map_tree_rows, min_offset=extra_offset_enter_dist, side=side,
+                             pose_type=ENTER_POSE)
+    start_out = get_car_outmost_pose(map_tree_rows, start_row_id, start_base[2], car, side=side, pose_type=LEAVE_POSE)
+    end_out = get_car_outmost_pose(map_tree_rows, end_row_id, end_base[2], car, side=side, pose_type=ENTER_POSE)
+    if side == NEAR_SIDE:
+        outmost_x = min(start_out[0], end_out[0])
+        start_xs = np.arange(start_base[0], outmost_x - accuracy, -accuracy)
+        end_xs = np.arange(end_base[0], outmost_x - accuracy, -accuracy)
+    else:
+        outmost_x = max(start_out[0], end_out[0])
+        start_xs = np.arange(start_base[0], outmost_x + accuracy, accuracy)
+        end_xs = np.arange(end_base[0], outmost_x + accuracy, accuracy)
+    return start_base, end_base, start_xs, end_xs
+
+
+def sample_start_end_pose_for_dubins(map_tree_rows, start_row_id, end_row_id, car, config_env, max_steer_angle=0.55,
+                                     plt=None, side=NEAR_SIDE, accuracy=0.2, extra_offset_enter_dist=0.0,
+                                     extra_offset_leave_dist=0.0):
+    """:457-555: every (exit x, entry x) pair; the feasible Dubins turn furthest inside the field boundary wins
+    (strict >: the first of equal scores).  None when no pair is feasible."""
+    start_base, end_base, start_xs, end_xs = _sample_x_lists(map_tree_rows, start_row_id, end_row_id, car, side,
+                                                             accuracy, extra_offset_enter_dist,
+                                                             extra_offset_leave_dist)
+    results = None
+    current = -np.inf
+    for sx in start_xs:
+        for ex in end_xs:
+            safe_start = np.array([sx, start_base[1], start_base[2]])
+            safe_end = np.array([ex, end_base[1], end_base[2]])
+            try:
+                path = get_dubins_path_full(safe_start, safe_end, 1.0 / car.curvature)
+            except (ValueError, IndexError, ZeroDivisionError):
+                path = None   # the reference's `turning_path is None`
+            if path is None:
+                continue
+            if config_env.check_path_feasibility(car, path[:, :3], boundary_check=False, aux_check=True):
+                dist = config_env.get_min_distance_to_boundary(car, path[:, :3], with_aux=True)
+                if dist > current:
+                    current = dist
+                    results = (safe_start, safe_end, abs(sx - start_base[0]), abs(ex - end_base[0]))
+    return results
+
+
+def sample_start_end_pose_for_reeds_shepp(map_tree_rows, start_row_id, end_row_id, car, config_env,
+                                          max_steer_angle=0.55, plt=None, side=NEAR_SIDE, accuracy=0.2,
+                                          extra_offset_enter_dist=0.0, extra_offset_leave_dist=0.0):
+    """:558-656: as the Dubins variant, a pair scoring the best of its feasible Reeds-Shepp words."""
+    start_base, end_base, start_xs, end_xs = _sample_x_lists(map_tree_rows, start_row_id, end_row_id, car, side,
+                                                             accuracy, extra_offset_enter_dist,
+                                                             extra_offset_leave_dist)
+    results = None
+    current = -np.inf
+    for sx in start_xs:
+        for ex in end_xs:
+            safe_start = np.array([sx, start_base[1], start_base[2]])
+            safe_end = np.array([ex, end_base[1], end_base[2]])
+            paths = get_all_reeds_shepp_paths_full(safe_start, safe_end, 1.0 / car.curvature)
+            best = -np.inf
+            if len(paths) == 0:
+                continue
+            for path in paths:
+                if config_env.check_path_feasibility(car, path[:, :3], boundary_check=False, aux_check=True):
+                    dist = config_env.get_min_distance_to_boundary(car, path[:, :3], with_aux=True)
+                    if dist > best:
+                        best = dist
+            if best > current:
+                current = best
+                results = (safe_start, safe_end, abs(sx - start_base[0]), abs(ex - end_base[0]))
+    return results
+
+
+def get_start_end_pose(map_tree_rows, start_row_id, end_row_id, side=NEAR_SIDE, extra_offset_enter_dist=0.4,
+                       extra_offset_leave_dist=1.1):
+    """:659-730: exit / entry poses at the outermost of the two row ends, moved out along the row heading."""
+    N, M = start_row_id, end_row_id
+    near_start = [(map_tree_rows[N, 0, 0] + map_tree_rows[N + 1, 0, 0]) / 2,
+                  (map_tree_rows[N, 0, 1] + map_tree_rows[N + 1, 0, 1]) / 2]
+    far_start = [(map_tree_rows[N, 1, 0] + map_tree_rows[N + 1, 1, 0]) / 2,
+                 (map_tree_rows[N, 1, 1] + map_tree_rows[N + 1, 1, 1]) / 2]
+    near_end = [(map_tree_rows[M, 0, 0] + map_tree_rows[M + 1, 0, 0]) / 2,
+                (map_tree_rows[M, 0, 1] + map_tree_rows[M + 1, 0, 1]) / 2]
+    far_end = [(map_tree_rows[M, 1, 0] + map_tree_rows[M + 1, 1, 0]) / 2,
+               (map_tree_rows[M, 1, 1] + map_tree_rows[M + 1, 1, 1]) / 2]
+    start_row_yaw = np.arctan2(far_start[1] - near_start[1], far_start[0] - near_start[0])
+    end_row_yaw = np.arctan2(far_end[1] - near_end[1], far_end[0] - near_end[0])
+    if side == NEAR_SIDE:
+        start_x = min(map_tree_rows[N, 0, 0], map_tree_rows[N + 1, 0, 0])
+        start_y = (map_tree_rows[N, 0, 1] + map_tree_rows[N + 1, 0, 1]) / 2
+        start_pose = [start_x - extra_offset_leave_dist * np.cos(start_row_yaw),
+                      start_y - extra_offset_leave_dist * np.sin(start_row_yaw), np.pi + start_row_yaw]
+        end_x = min(map_tree_rows[M, 0, 0], map_tree_rows[M + 1, 0, 0])
+        end_y = (map_tree_rows[M, 0, 1] + map_tree_rows[M + 1, 0, 1]) / 2
+        end_pose = [end_x - extra_offset_enter_dist * np.cos(end_row_yaw),
+                    end_y - extra_offset_enter_dist * np.sin(end_row_yaw), end_row_yaw]
+    if side == FAR_SIDE:
+        start_x = max(map_tree_rows[N, 1, 0], map_tree_rows[N + 1, 1, 0])
+        start_y = (map_tree_rows[N, 1, 1] + map_tree_rows[N + 1, 1, 1]) / 2
+        start_pose = [start_x + extra_offset_leave_dist * np.cos(start_row_yaw),
+                      start_y + extra_offset_leave_dist * np.sin(start_row_yaw), start_row_yaw]
+        end_x = max(map_tree_rows[M, 1, 0], map_tree_rows[M + 1, 1, 0])
+        end_y = (map_tree_rows[M, 1, 1] + map_tree_rows[M + 1, 1, 1]) / 2
+        end_pose = [end_x + extra_offset_enter_dist * np.cos(end_row_yaw),
+                    end_y + extra_offset_enter_dist * np.sin(end_row_yaw), end_row_yaw + np.pi]
+    return start_pose, end_pose
+
+
+def _circle_back_offsets(side, accuracy):
+    """:770-787: the offsets the while loop visits (accumulated by repeated addition, as the reference does) and
+    the offset it holds once exhausted."""
+    if not accuracy > 0:
+        raise ValueError("accuracy must be positive (the reference's loop would not end)")
+    step = -accuracy if side == NEAR_SIDE else accuracy
+    offsets, current = [], 0.0
+    while abs(current) < 5:
+        offsets.append(current)
+        current += step
+    return np.array(offsets), current
+
+
+def sample_start_end_pose_for_circle_back(map_tree_rows, start_row_id, end_row_id, car, config_env,
+                                          max_steer_angle=0.55, plt=None, side=NEAR_SIDE, accuracy=0.2,
+                                          extra_offset_enter_dist=0.0, extra_offset_leave_dist=0.0):
+    """:733-790: the exit pose moved outwards in steps of `accuracy` until the circle-back turn clears the rows.
+    Reference behaviour kept: when no offset below 5 m is feasible, the last pose tried is returned with the offset
+    the loop holds after it."""
+    start_base, end_base = get_start_end_pose(map_tree_rows, start_row_id, end_row_id, side,
+                                              extra_offset_enter_dist, extra_offset_leave_dist)
+    offsets, past = _circle_back_offsets(side, accuracy)
+    current = past
+    for off in offsets:
+        start_off = start_base + np.array([off, 0, 0])
+        path = get_circle_back_path_full(start_off, end_base, 1.0 / car.curvature, car, side)
+        if config_env.check_path_feasibility(car, path[:, :3], boundary_check=False, aux_check=True):
+            current = off
+            break
+    return (start_off, end_base, abs(current), 0.0)
+
+
+SAMPLE_TYPES = ("dubins", "reeds_shepp", "circle_back")
+
+
+def sample_turn(map_tree_rows, start_row_id, end_row_id, car, config_env, side=NEAR_SIDE, type="dubins",
+                accuracy=0.2, extra_offset_enter_dist=0.0, extra_offset_leave_dist=0.0):
+    """One request of sample_start_end_pose_batch as the device search takes it (_native.SamplePacked): base poses,
+    the x lists built exactly as the host functions build them, car, polygons.  `past` is the circle-back loop's
+    offset once exhausted."""
+    if type not in SAMPLE_TYPES:
+        raise ValueError("unknown sampling type %r" % (type,))
+    past = 0.0
+    if type == "circle_back":
+        start_base, end_base = get_start_end_pose(map_tree_rows, start_row_id, end_row_id, side,
+                                                  extra_offset_enter_dist, extra_offset_leave_dist)
+        start_base, end_base = np.array(start_base, dtype=np.float64), np.array(end_base, dtype=np.float64)
+        offsets, past = _circle_back_offsets(side, accuracy)
+        start_xs = np.array([(start_base + np.array([off, 0, 0]))[0] for off in offsets])
+        end_xs = np.array([end_base[0]])
+    else:
+        start_base, end_base, start_xs, end_xs = _sample_x_lists(map_tree_rows, start_row_id, end_row_id, car, side,
+                                                                 accuracy, extra_offset_enter_dist,
+                                                                 extra_offset_leave_dist)
+    return dict(type=type, side=side, start=start_base, end=end_base, start_x=start_xs, end_x=end_xs,
+                wheel_base=car.WHEEL_BASE, max_steer=car.MAX_STEER, radius=1.0 / car.curvature, step=0.1,
+                body=ring_of(car.car_poly), aux=[ring_of(a) for a in car.aux_polys],
+                blockers=[ring_of(q) for q in config_env.obs_poly_list], field=ring_of(config_env.field_range_poly),
+                past=past)
+
+
+def sample_result_tuple(turn, status, poses):
+    """The reference's return value of one searched turn from the device outputs (status, poses[8])."""
+    from .. import _native
+    if turn["type"] == "circle_back":
+        offset = poses[6] if status == _native.SMP_OK else abs(turn["past"])
+        return (np.array(poses[0:3]), np.array(turn["end"], dtype=np.float64), float(offset), 0.0)
+    if status != _native.SMP_OK:
+        return None
+    return (np.array(poses[0:3]), np.array(poses[3:6]), float(poses[6]), float(poses[7]))
+
+
+def sample_start_end_pose_batch(requests, device=None, **opts):
+    """The sampled pose search for many turns in one launch.  A request is a dict with the arguments of the
+    sample_start_end_pose_for_* functions: map_tree_rows, start_row_id, end_row_id, car, config_env, and optionally
+    side, type ("dubins" / "reeds_shepp" / "circle_back"), accuracy, extra_offset_enter_dist,
+    extra_offset_leave_dist.  Returns, per request, what the function of its type returns (a tuple, or None).
+    `device`: a _native.Context, a device index, or None for device 0.  A turn the kernel could not search (overflow,
+    bad input) raises."""
+    from .. import _native
+    turns = [sample_turn(**r) for r in requests]
+    if not turns:
+        return []
+    ctx = device if isinstance(device, _native.Context) else _native.Context(0 if device is None else int(device))
+    res = ctx.classic_sample(_native.SamplePacked(turns, **opts), tables=False)
+    out = []
+    for k, t in enumerate(turns):
+        st = int(res.status[k])
+        if st not in (_native.SMP_OK, _native.SMP_NONE_FEASIBLE):
+            raise RuntimeError("[htp] sampled pose search: turn %d ended %s" % (k, _native.SMP_STATUS[st]))
+        out.append(sample_result_tuple(t, st, res.poses[k]))
+    return out

@@ -1045,6 +1045,87 @@ int htp_classic_turn_batch_device(htp_ctx* ctx, const htp_classic_batch* in, htp
 double htp_classic_last_ms(htp_ctx* ctx);
 
 /* ---------------------------------------------------------------------------
+ * Sampled exit / entry pose search of the classic turns (safety_forward_path_plan.py:457-790, the
+ * sample_start_end_pose_for_dubins / _reeds_shepp / _circle_back variants; csrc/sample_core.h).
+ *
+ * Candidate.  A turn has base poses start = (sx, sy, syaw), end = (ex, ey, eyaw) and lists start_x[n_start],
+ *   end_x[n_end].  Candidate (i, j) is start with x = start_x[i] and end with x = end_x[j]; its flattened index is
+ *   i * n_end + j (the reference's loop order: start outer, end inner).  The caller builds the lists (np.arange, as
+ *   the reference does); the kernel only consumes them.
+ * Path of a candidate (R = params[RADIUS], the caller passes 1 / car.curvature; step = params[STEP], 0.1):
+ *   HTP_SMP_DUBINS       get_dubins_path_full(start, end, R, step)
+ *   HTP_SMP_REEDS_SHEPP  every word of calc_all_paths(start, end, 1 / R, step), sampled as the fish-tail samples them
+ *   HTP_SMP_CIRCLE_BACK  get_circle_back_path_full(start, end, R, car, side, step); n_end == 1
+ * Feasible = check_path_feasibility(car, path, boundary_check=False, aux_check=True): the body at every path row and
+ *   each implement at every second row (rows 0, 2, 4, ... as get_path_poly places them) disjoint from every blocker
+ *   under the closed-set separating-axis predicate of the other planners (touching collides).  No field containment.
+ * Score = get_min_distance_to_boundary(car, path, with_aux=True): the minimum, over all corners of the body placed at
+ *   every row and of each implement placed at every second row, of the signed distance to the field ring: Euclidean
+ *   distance to the nearest ring segment, positive when the corner is inside the ring by the crossing-number rule of
+ *   the searches' field test, negative otherwise.
+ *   A Reeds-Shepp candidate scores the maximum over its feasible words; without a feasible word it is infeasible.
+ * Winner.  Dubins / Reeds-Shepp: the feasible candidate with the largest score, ties to the lowest flattened index
+ *   (the reference's strict >); none feasible: HTP_SMP_NONE_FEASIBLE (the reference returns None).  Circle-back: the
+ *   first feasible candidate in index order; none feasible: the LAST candidate is reported with
+ *   HTP_SMP_NONE_FEASIBLE (the reference's exhausted while loop returns the last pose it tried).
+ * Deviation from the reference, stated: the reference scores exterior.coords of the shapely unary_union of the placed
+ *   polygons; this scores every corner of every placed polygon.  For a CONVEX field ring the two minima are the same
+ *   number (the signed distance to a convex set is concave, so its minimum over the swept region is attained at an
+ *   extreme point of the region's hull, which is a placed corner on the union's exterior).  For a non-convex ring
+ *   (get_map_exterior_pts with l_std > 0) they can differ: the reference adds edge-crossing points and drops interior
+ *   corners.  The reference itself (shapely, pydubins) was not run against this; the numpy restatement in
+ *   path_planner/safety_forward_path_plan.py is the oracle of the tests.
+ * The body and the implements are 4-vertex polygons (car_model.py builds rectangles only).  Per turn, the body, the
+ *   implements, the blockers and the field ring together hold at most HTP_SMP_MAX_POLY polygons and
+ *   HTP_SMP_MAX_VERT vertices (they are staged in LDS); more is HTP_SMP_BAD_INPUT.
+ * The winner's path is not an output: feed the safe poses to htp_classic_turn_batch. */
+#define HTP_SMP_NDESC 6
+#define HTP_SMP_NPOSE 8
+#define HTP_SMP_MAX_POLY 48
+#define HTP_SMP_MAX_VERT 256
+enum { HTP_SMP_D_BODY = 0, HTP_SMP_D_AUX0, HTP_SMP_D_AUX1 /* implement polygon ids, -1: none */,
+       HTP_SMP_D_BLK0, HTP_SMP_D_BLK1 /* blockers [blk0, blk1) */, HTP_SMP_D_FIELD /* field ring */ };
+enum { HTP_SMP_DUBINS = 0, HTP_SMP_REEDS_SHEPP = 1, HTP_SMP_CIRCLE_BACK = 2 };
+/* turn status.  OVERFLOW: n_start * n_end > cap_cand, or a candidate's path outgrew cap_samples (the winner among the
+ * remaining candidates is still reported).  BAD_INPUT: non-finite base pose or car parameter, n_start or n_end out of
+ * [1, cap], circle-back with n_end != 1, unknown type or side, polygons out of range or over the LDS capacity. */
+enum { HTP_SMP_OK = 0, HTP_SMP_NONE_FEASIBLE = 1, HTP_SMP_OVERFLOW = 2, HTP_SMP_BAD_INPUT = 3 };
+/* candidate status.  PLANNER: no Dubins path / no Reeds-Shepp word, or the reference would raise in reeds_shepp.
+ * OVERFLOW: a path longer than cap_samples.  BAD_INPUT: a non-finite x sample.  UNUSED: a table slot past
+ * n_start * n_end, or any slot of a turn that ended OVERFLOW (table) or BAD_INPUT. */
+enum { HTP_SMP_C_FEASIBLE = 0, HTP_SMP_C_BLOCKED = 1, HTP_SMP_C_PLANNER = 2, HTP_SMP_C_OVERFLOW = 3,
+       HTP_SMP_C_BAD_INPUT = 4, HTP_SMP_C_UNUSED = 5 };
+typedef struct {
+  int32_t batch, npoly, nvert;
+  const double* params;     /* [batch][HTP_CT_NPARAM], the HTP_CT_P_* layout with TYPE = HTP_SMP_* */
+  const int32_t* desc;      /* [batch][HTP_SMP_NDESC] polygon ids */
+  const int32_t* poly_off;  /* [npoly+1] */
+  const double* vertices;   /* [nvert][2] */
+  const double* start_x;    /* [batch][cap_s] */
+  const double* end_x;      /* [batch][cap_e] */
+  const int32_t* n_start;   /* [batch] */
+  const int32_t* n_end;     /* [batch] */
+  int32_t cap_s, cap_e;
+  int32_t cap_cand;         /* candidate table slots per turn: n_start * n_end <= cap_cand */
+  int32_t cap_samples;      /* path rows / Dubins samples per candidate (scratch sizing), >= 16 */
+  int32_t max_groups;       /* workgroups of each candidate kernel; 0: as many as are resident at once */
+} htp_classic_sample_in;
+typedef struct {
+  int32_t* status;          /* [batch] HTP_SMP_* */
+  int32_t* winner;          /* [batch][2] i, j (-1, -1 where there is none) */
+  double* poses;            /* [batch][HTP_SMP_NPOSE] safe start x, y, yaw, safe end x, y, yaw, leave_offset,
+                               enter_offset (|x - base x|); NaN where there is no winner */
+  double* score;            /* [batch] the winner's score (-inf where there is none) */
+  int32_t* n_feasible;      /* [batch] */
+  double* cand_score;       /* [batch][cap_cand] score, -inf where not feasible (nullable) */
+  int32_t* cand_status;     /* [batch][cap_cand] HTP_SMP_C_* (nullable) */
+} htp_classic_sample_result;
+int htp_classic_sample_batch(htp_ctx* ctx, const htp_classic_sample_in* in, htp_classic_sample_result* out);
+int htp_classic_sample_batch_device(htp_ctx* ctx, const htp_classic_sample_in* in, htp_classic_sample_result* out,
+                                    void* stream);
+double htp_classic_sample_last_ms(htp_ctx* ctx);   /* candidate kernels + winner kernel of the last launch */
+
+/* ---------------------------------------------------------------------------
  * Orchard workload chain on the device (synth.make_orchard_instance's steps after the scene draws): for each
  * problem, the classic turn (htp_classic_turn_batch) -> get_init_ref_path at spacing ds / 2 = L / (2N - 2)
  * (ds = L / (N - 1), the resampled spacing), desired_v = min(ds / dT, 0.9) (R/obca_py/util.py:62-113) -> the init guess resampled to N rows and the
