@@ -1527,8 +1527,8 @@ class ClassicPacked:
 
 
 class ClassicResults:
-    def __init__(self, packed):
-        B = packed.batch
+    def __init__(self, packed, rows=None):
+        B = packed.batch if rows is None else int(rows)   # rows: storage for more turns than the batch has
         self.status = np.zeros(B, np.int32)
         self.n_path = np.zeros(B, np.int32)
         self.path = np.zeros((B, packed.cap_path, 5))
@@ -1797,13 +1797,22 @@ class Context:
             raise RuntimeError(f"[htp] htp_obca_points_solve_batch failed: {self.error()}")
         return res
 
-    def classic_turns(self, packed):
-        """Batched classic headland turns (host buffers) -> ClassicResults."""
-        r = ClassicResults(packed)
+    def classic_turns(self, packed, out=None):
+        """Batched classic headland turns (host buffers) -> ClassicResults.  `out`: a ClassicResults to fill; what the
+        kernel leaves unwritten (rows from n_path on, the rows of a rejected turn) stays as it was."""
+        r = ClassicResults(packed) if out is None else out
         b, rs = packed.struct(), r.struct()
         if self.lib.htp_classic_turn_batch(self.ctx, ctypes.byref(b), ctypes.byref(rs)) != 0:
             raise RuntimeError(f"[htp] htp_classic_turn_batch failed: {self.error()}")
         return r
+
+    def classic_turns_device(self, packed, dev_ptrs, out_ptrs, stream=None):
+        """Device-resident classic turns on `stream`, not synchronised.  dev_ptrs: device pointers of the
+        ClassicPacked arrays by name; out_ptrs: those of status, n_path and path.  The polygon ids are trusted."""
+        b = packed.struct(dev_ptrs)
+        r = CtResult(out_ptrs["status"], out_ptrs["n_path"], out_ptrs["path"])
+        if self.lib.htp_classic_turn_batch_device(self.ctx, ctypes.byref(b), ctypes.byref(r), stream) != 0:
+            raise RuntimeError(f"[htp] htp_classic_turn_batch_device failed: {self.error()}")
 
     def classic_last_ms(self):
         return self.lib.htp_classic_last_ms(self.ctx)

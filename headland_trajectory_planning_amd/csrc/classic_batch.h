@@ -11,9 +11,20 @@ template <class C>
 HTP_HD inline void run_problem(C& c, const htp_classic_batch& in, const htp_classic_result& out, int64_t b,
                                double* scr, rs::Path* paths, int* flags) {
   const double* p = in.params + b * HTP_CT_NPARAM;
+  // judged before anything is converted or planned: every parameter finite, type and side small enough to cast
+  // (beyond int the conversion differs between the host and the device), the steering limit within (0, 1.5) as
+  // the sample kernel's turn_info has it, a side the circle-back and fish-tail planners know
+  bool ok = true;
+  for (int j = 0; j < HTP_CT_NPARAM; ++j) ok = ok && p[j] - p[j] == 0.0;
+  ok = ok && fabs(p[HTP_CT_P_TYPE]) < 1e9 && fabs(p[HTP_CT_P_SIDE]) < 1e9;
+  ok = ok && p[HTP_CT_P_MAXSTEER] > 0.0 && p[HTP_CT_P_MAXSTEER] < 1.5;
+  // ... and large enough to steer with: a minimum turning radius wb / tan(max_steer) beyond MAX_TURN_RADIUS is an
+  // input error, not a turn that more capacity would plan
+  if (ok && !(p[HTP_CT_P_WB] <= MAX_TURN_RADIUS * hm::tan(p[HTP_CT_P_MAXSTEER]))) ok = false;
   Spec sp;
-  sp.type = (int)p[HTP_CT_P_TYPE];
-  sp.side = (int)p[HTP_CT_P_SIDE];
+  sp.type = ok ? (int)p[HTP_CT_P_TYPE] : -1;
+  sp.side = ok ? (int)p[HTP_CT_P_SIDE] : 0;
+  if (sp.type != T_DUBINS && sp.side != NEAR_SIDE && sp.side != FAR_SIDE) ok = false;
   for (int j = 0; j < 3; ++j) {
     sp.start[j] = p[HTP_CT_P_SX + j];
     sp.end[j] = p[HTP_CT_P_EX + j];
@@ -35,7 +46,7 @@ HTP_HD inline void run_problem(C& c, const htp_classic_batch& in, const htp_clas
   fp.lane0 = 0;
   fp.lane1 = 0;
   Turn<C> T{c, sp, fp, scr, in.cap_samples, out.path + b * (int64_t)in.cap_path * 5, in.cap_path, paths, flags};
-  if (fp.nb < 3 || fp.nb > ha::MAXB) T.status = ST_BAD_INPUT;
+  if (!ok || fp.nb < 3 || fp.nb > ha::MAXB) T.status = ST_BAD_INPUT;
   else T.run();
   if (c.lane == 0) {
     out.status[b] = T.status;

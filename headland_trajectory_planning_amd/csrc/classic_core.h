@@ -36,7 +36,8 @@ enum { T_DUBINS = 0, T_CIRCLEBACK = 1, T_FISHTAIL = 2 };
 enum { ST_OK = 0, ST_OVERFLOW = 1, ST_NO_WORD = 2, ST_BAD_INPUT = 3, ST_RS_ERROR = 4, ST_NO_DUBINS = 5 };
 enum { NEAR_SIDE = 1, FAR_SIDE = 2, LEAVE_POSE = 1, ENTER_POSE = 2 };   // map_utils constants
 constexpr double PI = 3.141592653589793;
-constexpr int SCR_PER_POINT = 10;   // Dubins scratch: T X Y S DX DY + 4 tridiagonal work
+constexpr double MAX_TURN_RADIUS = 1.0e6;   // metres; run_problem rejects a steering limit that cannot do better
+constexpr int SCR_PER_POINT = 10;  // Dubins scratch: T X Y S DX DY + 4 tridiagonal work
 
 HTP_HD inline double wrap(double a) { return rs::pymod(a + PI, 2.0 * PI) - PI; }   // angle_wrap
 HTP_HD inline double sgnf(double v) { return v > 0 ? 1.0 : (v < 0 ? -1.0 : 0.0); }
@@ -138,19 +139,28 @@ struct Turn {
   }
 
   // calculate_motion_path_new(init_pose, motion_dir, steer_dir, turning_radius, delta_yaw, step) car_model.py:236-269
+  // np.linspace's sample count of one such arc, int(arc / step), as a double (NaN when the arc is)
+  HTP_HD double arc_steps(double R, double dyaw, double step) const {
+    const double tr = fmax(1.0 / curvature(), R);
+    return floor(fabs(dyaw * tr) / step);
+  }
+
   HTP_HD int arc_new(const double* p0, double mdir, double sdir, double R, double dyaw, double step, int row0) {
     const double tr = fmax(1.0 / curvature(), R);
     const double steer = hm::atan(sp.wb / tr) * sdir;
     const double arc = fabs(dyaw * tr);
-    const int num = (int)(arc / step);
-    if (num < 1) { status = ST_BAD_INPUT; return -1; }
+    // the sample count is judged as a double: a quotient beyond int (a tiny step) converts differently on the host
+    // (INT_MIN) and on the device (INT_MAX), and the capacity test below would wrap; only a count that fits is cast
+    const double qn = arc_steps(R, dyaw, step);
+    if (!(qn >= 1.0)) { status = ST_BAD_INPUT; return -1; }
+    if (qn > (double)(cap_out - row0 - 2)) { status = ST_OVERFLOW; return -1; }
+    const int num = (int)qn;
     const double act = arc / num;
     const double ystep = mdir * act / sp.wb * hm::tan(steer);
     const double iy = wrap(p0[2]);
     const double stop = iy + ystep * num;
     const double lstep = (stop - iy) / num;
     const double kap = fabs(steer) > 0.00001 ? hm::tan(steer) / sp.wb : 0.0;
-    if (row0 + num + 2 > cap_out) { status = ST_OVERFLOW; return -1; }
     if (c.lane == 0) put_row(row0, p0[0], p0[1], p0[2], kap, mdir);
     for (int k = c.lane; k <= num; k += C::width) {
       const double yl = k == num ? stop : (double)k * lstep + iy;   // np.linspace
@@ -172,12 +182,15 @@ struct Turn {
     const double mdir = pose_type == ENTER_POSE ? -1.0 : 1.0, odir = pose_type == ENTER_POSE ? -1.0 : 1.0;
     const double st = 0.55 * turn_dir, step = 0.1, dyaw = 0.7853981633974483;   // math.radians(45)
     const double search_len = dyaw / curvature();
-    const int num = (int)rint(search_len / step);
+    // as in arc_new: the scan length is judged as a double (max_steer -> 0 makes it unbounded), then cast
+    const double qn = rint(search_len / step);
+    if (qn < 0.0) { status = ST_BAD_INPUT; return; }
+    if (!(qn <= (double)(cap_scr - 1))) { status = ST_OVERFLOW; return; }   // NaN and +inf included
+    const int num = (int)qn;
     const double ystep = mdir * step / sp.wb * hm::tan(st);
     double* PX = scr;
     double* PY = scr + cap_scr;
     double* PW = scr + 2 * cap_scr;
-    if (num + 1 > cap_scr) { status = ST_OVERFLOW; return; }
     for (int kd = 0; kd < 51; ++kd) {   // np.arange(0, max_offset + accuracy, accuracy)
       const double dist = 0.0 + (double)kd * 0.1;
       const double x0 = init[0] + dist * hm::cos(init[2]) * odir, y0 = init[1] + dist * hm::sin(init[2]) * odir;
@@ -330,6 +343,12 @@ struct Turn {
       if (sp.side == FAR_SIDE && s0[0] + (Rf + Rb) * hm::cos(theta - PI / 2) > e0[0] + sp.step) break;
       Rf *= 1.05;
       Rb *= 1.05;
+    }
+    // an arc shorter than one step (the reference divides by zero) or not a number is bad input: both arcs are
+    // judged before the first writes a row, so a rejected turn leaves its rows as they were
+    if (!(arc_steps(Rf, theta, sp.step) >= 1.0) || !(arc_steps(Rb, PI - theta, sp.step) >= 1.0)) {
+      status = ST_BAD_INPUT;
+      return;
     }
     const double td = enter_steer_dir(s0, e0);
     int row = 0;

@@ -89,6 +89,11 @@ int htp_classic_turn_batch(htp_ctx* ctx, const htp_classic_batch* in, htp_classi
   H2D(o_d, in->desc, 12 * (size_t)B);
   H2D(o_po, in->poly_off, 4 * (size_t)(in->npoly + 1));
   H2D(o_v, in->vertices, 16 * (size_t)in->nvert);
+  // the caller's outputs go up too: what the kernel leaves unwritten (rows from n_path on, the rows of a rejected
+  // turn) comes back as the caller had it, as with the device entry, not as whatever the allocation held
+  H2D(o_st, out->status, 4 * (size_t)B);
+  H2D(o_np, out->n_path, 4 * (size_t)B);
+  H2D(o_pa, out->path, 40 * (size_t)B * (size_t)in->cap_path);
   htp_classic_batch din = *in;
   din.params = (const double*)(d + o_p);
   din.desc = (const int32_t*)(d + o_d);

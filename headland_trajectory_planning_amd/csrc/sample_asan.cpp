@@ -154,6 +154,20 @@ int main() {
     in = B.in();
     expect(htp_hostsim_classic_sample(&in, &r, msg, sizeof msg) == -1, "a polygon id out of range is refused");
   }
+  {   // a circle-back turn whose step makes an arc of 6e9 samples: judged as a double, an overflow, never converted
+    Batch B(3, 1, 3, 64);
+    B.turn(HTP_SMP_CIRCLE_BACK, 1, 1.5, 4.5, 3, 1, -1.0, -1.5, false, false);
+    B.turn(HTP_SMP_CIRCLE_BACK, 1, 1.5, 4.5, 3, 1, -1.0, -1.5, false, false);
+    B.params[1 * HTP_CT_NPARAM + HTP_CT_P_STEP] = 1e-9;
+    htp_classic_sample_in in = B.in();
+    Out O(B.batch, B.cap_cand);
+    htp_classic_sample_result r = O.res();
+    expect(htp_hostsim_classic_sample(&in, &r, msg, sizeof msg) == 0, "the tiny-step batch runs");
+    std::printf("tiny step: status %d, candidates %d %d %d\n", O.status[1], O.cand_status[3], O.cand_status[4],
+                O.cand_status[5]);
+    expect(O.status[1] == HTP_SMP_OVERFLOW, "a step of 1e-9: overflow");
+    for (int k = 0; k < 3; ++k) expect(O.cand_status[3 + k] == HTP_SMP_C_OVERFLOW, "a step of 1e-9: candidate overflow");
+  }
   std::printf(fails ? "%d check(s) failed\n" : "all checks passed\n", fails);
   return fails ? 1 : 0;
 }

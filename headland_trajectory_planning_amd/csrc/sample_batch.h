@@ -58,6 +58,8 @@ HTP_HD inline int poly_len(const htp_classic_sample_in& in, int p) {   // -1: id
 }
 
 // What one turn is, checked: ST_OK, or the status it ends with before any candidate is planned.  Uniform.
+// max_steer is held to (0, 1.5) as in ct::run_problem, but not to its ct::MAX_TURN_RADIUS bound: a steering limit
+// that small is planned here, and its candidates end as the planner has them (C_OVERFLOW).
 struct TurnInfo {
   int status, type, ns, ne, ncand, naux, aux0, aux1;   // aux0 / aux1: the implements present, in order
   ct::Spec sp;

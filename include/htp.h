@@ -1018,7 +1018,27 @@ double htp_oge_last_ms(htp_ctx* ctx);
  *   HTP_CT_FISHTAIL    get_start_end_pose_for_reeds_shepp (:300-364) + the collision-free Reeds-Shepp word
  *                      with the least backward length + Dubins lead-in/out (R/test/classic_planner.ipynb 10-11)
  * Footprints (fish-tail only): the body polygon at every pose against the blocker polygons
- * (check_path_feasibility :423-458, boundary_check=False); polygons in CSR pools as for the searches. */
+ * (check_path_feasibility :423-458, boundary_check=False); polygons in CSR pools as for the searches.
+ *
+ * Status of a turn (n_path is 0 unless HTP_CT_OK):
+ *   HTP_CT_BAD_INPUT  judged before anything is planned, the turn's rows of `path` are left as they were: a
+ *                     parameter that is not finite; max_steer outside (0, 1.5) or so small that the minimum
+ *                     turning radius wheel_base / tan(max_steer) exceeds 1e6 m; a type other than HTP_CT_*; for
+ *                     the circle-back and fish-tail types a side other than 1 / 2; wheel_base, radius or step not
+ *                     positive; a body polygon of fewer than 3 or more than HTP_HA_MAX_BODY vertices; a circle-back
+ *                     arc shorter than one step (the reference divides by zero there).
+ *   HTP_CT_OVERFLOW   a sample or row count exceeds its capacity: Dubins samples or the fish-tail's turn-out scan
+ *                     against cap_samples, the rows of an arc, a Dubins piece or the Reeds-Shepp word against
+ *                     cap_path.  Counts are compared as doubles before they are converted, so a step of 1e-9 is an
+ *                     overflow like any other.  The pieces that fitted before the one that did not may have been
+ *                     written: rows of the turn's own [cap_path] block are unspecified, nothing outside it changes.
+ *   HTP_CT_NO_WORD    no collision-free Reeds-Shepp word; HTP_CT_RS_ERROR the reference raises in reeds_shepp (nearly
+ *                     coincident poses).  No row is written.
+ *   HTP_CT_NO_DUBINS  no Dubins word, or a path of fewer than two distinct samples (start == end).  The Dubins type
+ *                     writes no row; in the circle-back and fish-tail types the pieces before the failing Dubins
+ *                     piece may have been written, as for HTP_CT_OVERFLOW.
+ * Of a HTP_CT_OK turn rows [0, n_path) are written, the rows from n_path on are left as they were.  Both entries keep
+ * to this: htp_classic_turn_batch hands the caller's `path`, `status` and `n_path` to the device and back. */
 #define HTP_CT_NPARAM 12
 enum { HTP_CT_P_TYPE = 0, HTP_CT_P_SIDE,                      /* HTP_CT_* ; map_utils NEAR_SIDE 1 / FAR_SIDE 2 */
        HTP_CT_P_SX, HTP_CT_P_SY, HTP_CT_P_SYAW, HTP_CT_P_EX, HTP_CT_P_EY, HTP_CT_P_EYAW,
@@ -1088,7 +1108,9 @@ enum { HTP_SMP_D_BODY = 0, HTP_SMP_D_AUX0, HTP_SMP_D_AUX1 /* implement polygon i
 enum { HTP_SMP_DUBINS = 0, HTP_SMP_REEDS_SHEPP = 1, HTP_SMP_CIRCLE_BACK = 2 };
 /* turn status.  OVERFLOW: n_start * n_end > cap_cand, or a candidate's path outgrew cap_samples (the winner among the
  * remaining candidates is still reported).  BAD_INPUT: non-finite base pose or car parameter, n_start or n_end out of
- * [1, cap], circle-back with n_end != 1, unknown type or side, polygons out of range or over the LDS capacity. */
+ * [1, cap], circle-back with n_end != 1, unknown type or side, polygons out of range or over the LDS capacity,
+ * max_steer outside (0, 1.5).  htp_classic_turn_batch's further bound on max_steer (a minimum turning radius of at
+ * most 1e6 m) is not applied here: a smaller max_steer is planned and ends as the planner has it (C_OVERFLOW). */
 enum { HTP_SMP_OK = 0, HTP_SMP_NONE_FEASIBLE = 1, HTP_SMP_OVERFLOW = 2, HTP_SMP_BAD_INPUT = 3 };
 /* candidate status.  PLANNER: no Dubins path / no Reeds-Shepp word, or the reference would raise in reeds_shepp.
  * OVERFLOW: a path longer than cap_samples.  BAD_INPUT: a non-finite x sample.  UNUSED: a table slot past

@@ -273,12 +273,13 @@ def chain_host(inputs, platform=False):
     return insts, status
 
 
-def classic_host(packed, platform=False):
-    """classic_core.h through the serial host build (same batch/result structs as the GPU).  TEST-ONLY."""
+def classic_host(packed, platform=False, out=None):
+    """classic_core.h through the serial host build (same batch/result structs as the GPU).  `out`: a
+    ClassicResults to fill (pre-filled by the caller).  TEST-ONLY."""
     L = lib(platform)
     L.htp_hostsim_classic.argtypes = [ctypes.POINTER(_native.CtBatch), ctypes.POINTER(_native.CtResult)]
     L.htp_hostsim_classic.restype = ctypes.c_int
-    res = _native.ClassicResults(packed)
+    res = _native.ClassicResults(packed) if out is None else out
     b, r = packed.struct(), res.struct()
     assert L.htp_hostsim_classic(ctypes.byref(b), ctypes.byref(r)) == 0
     return res

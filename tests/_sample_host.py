@@ -42,11 +42,12 @@ def build():
 
 
 def build_asan():
-    """csrc/sample_asan.cpp (its own main) with -fsanitize=address,undefined: a plain executable."""
+    """csrc/sample_asan.cpp (its own main) with -fsanitize=address,undefined,float-cast-overflow (GCC's `undefined`
+    group leaves the last out): a plain executable."""
     os.makedirs(os.path.dirname(ASAN_EXE), exist_ok=True)
     if _fresh(ASAN_EXE, _deps(("sample_asan.cpp",))):
         return ASAN_EXE
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined",
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined,float-cast-overflow",
                            "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-o", ASAN_EXE,
                            os.path.join(CSRC, "sample_asan.cpp")])
     return ASAN_EXE

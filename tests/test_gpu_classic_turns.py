@@ -39,3 +39,186 @@ def test_gpu_matches_host_core(ctx):
     for b, p in enumerate(paths):
         ref = get_init_ref_path(car, p[:, 0], p[:, 1], p[:, 2], p[:, 3], p[:, 4], desired_v=0.5, ds=0.2)
         assert np.max(np.abs(rp.path(b) - ref)) < 1e-9
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The planner at its edges (tests/_classic_cases.py: every status, each capacity check, bad input of every kind), the
+# device against the host build.  The batch is the one tests/test_classic_edges_cpu.py runs through the stand-alone
+# sanitizer program, so the device sees no input that program has not passed.  Outputs are pre-filled with
+# sentinels and carry one turn of storage beyond the batch.  A launch is at most 65 wavefronts with 256 rows and
+# 512 samples a turn.
+import _classic_cases as cc
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.int64) if a.dtype == np.float64 else a
+
+
+_edge = {}
+
+
+def _edge_case():
+    """(cases, packed, host build's results): computed once, shared, left unchanged."""
+    if not _edge:
+        cases = cc.edge_batch()
+        pk = cc.pack(cases)
+        _edge["v"] = (cases, pk, H.classic_host(pk, out=cc.sentinel_results(pk)))
+    return _edge["v"]
+
+
+@pytest.fixture(scope="module")
+def first(ctx):
+    """The edge batch's first launch through the staged entry."""
+    _, pk, _ = _edge_case()
+    return ctx.classic_turns(pk, out=cc.sentinel_results(pk))
+
+
+def test_edge_batch_equals_host_build(first):
+    cases, pk, host = _edge_case()
+    B = pk.batch
+    names = [_native.CT_STATUS.get(int(s), int(s)) for s in first.status[:B]]
+    print("device statuses:", list(zip([c[0] for c in cases], names, first.n_path[:B].tolist())))
+    assert np.array_equal(first.status, host.status), [(b, cases[b][0], names[b]) for b in range(B) if first.status[b] != host.status[b]]
+    assert np.array_equal(first.n_path, host.n_path)
+    assert names == [c[3] for c in cases]
+    worst = 0.0
+    for b, c in enumerate(cases):
+        n = int(host.n_path[b])
+        if c[3] == "ok":
+            worst = max(worst, float(np.max(np.abs(first.path[b, :n] - host.path[b, :n]))))
+            assert np.all(first.path[b, n:] == cc.SENTINEL), (b, c[0])       # as the host build leaves them
+        elif c[3] != "overflow":     # an overflowing turn may have written some of its own rows (include/htp.h)
+            assert np.array_equal(_bits(first.path[b]), _bits(host.path[b])), (b, c[0])
+            assert np.all(first.path[b] == cc.SENTINEL), (b, c[0])
+    print(f"largest device-host row difference over the good turns: {worst:.3e}")
+    assert worst <= 1e-12, worst
+    assert first.status[B] == cc.ISENTINEL and first.n_path[B] == cc.ISENTINEL and np.all(first.path[B] == cc.SENTINEL)
+    assert B == 65
+    # rows 2R apart: the circle-back type is the Dubins type, bit for bit, on the device too
+    at = {c[0]: b for b, c in enumerate(cases)}
+    a, d = at["cb rows 2R apart"], at["db rows 2R apart"]
+    assert first.n_path[a] > 0 and np.array_equal(_bits(first.path[a]), _bits(first.path[d]))
+
+
+def _compare_launch(g, host, cases, name):
+    """A launch against the host build: statuses, counts and the places that still hold the sentinel exactly, the
+    written rows within 1e-12, the turn of storage beyond the batch untouched."""
+    B = len(cases)
+    assert np.array_equal(g.status, host.status) and np.array_equal(g.n_path, host.n_path), (name, g.status, host.status)
+    assert [_native.CT_STATUS.get(int(s)) for s in g.status[:B]] == [c[3] for c in cases], name
+    kept = host.path == cc.SENTINEL
+    assert np.array_equal(g.path == cc.SENTINEL, kept), name
+    worst = float(np.max(np.abs(g.path[~kept] - host.path[~kept]))) if (~kept).any() else 0.0
+    print(f"{name}: statuses {g.status[:B].tolist()} rows {g.n_path[:B].tolist()}, "
+          f"largest device-host difference {worst:.3e}")
+    assert worst <= 1e-12, (name, worst)
+    for b, c in enumerate(cases):
+        if c[3] == "ok":
+            assert np.all(kept[b, int(host.n_path[b]):]) and not np.any(kept[b, :int(host.n_path[b])]), (name, b)
+    assert g.status[B] == cc.ISENTINEL and g.n_path[B] == cc.ISENTINEL and np.all(kept[B]), name
+
+
+def test_capacity_edges_equal_host_build(ctx):
+    """The capacity checks at their edges (arc_new's rows, dubins_full's rows and samples, the fish-tail word's
+    rows): ten launches of three or four turns with cap_path at a turn's row count, one below it and at the
+    circle-back's partial counts, and cap_samples = 16 with 16 and 17 Dubins samples.  A turn that fills its block
+    to the last row has the next turn's block directly behind it; every block is compared, the written rows of an
+    overflowing turn too (what the host build wrote, the device wrote)."""
+    filled = 0
+    for name, cases, cap_path, cap_samples in cc.capacity_launches():
+        pk = cc.pack(cases, cap_path, cap_samples)
+        host = H.classic_host(pk, out=cc.sentinel_results(pk))
+        g = ctx.classic_turns(pk, out=cc.sentinel_results(pk))
+        _compare_launch(g, host, cases, name)
+        filled += int(np.sum(host.n_path[:pk.batch] == cap_path))
+    assert filled >= 4      # the circle-back turn twice in its launch, the fish-tail and the Dubins turn once each
+
+
+@pytest.mark.parametrize("size", [65, 63, 1])
+def test_placement_does_not_show(ctx, first, size):
+    """The batch reversed (65), reversed without the two turns that then come first (63: every turn but the last
+    two, at another block index), and the tiny-step circle-back turn alone: every turn's outputs are those of the
+    first launch, bit for bit (block index and the per-wave scratch offset ws + b * SCR_PER_POINT * cap_samples
+    leak nothing)."""
+    cases, pk, _ = _edge_case()
+    idx = {65: list(range(pk.batch))[::-1], 63: list(range(pk.batch))[::-1][2:], 1: [1]}[size]
+    assert len(idx) == size and cases[1][0] == "cb step 1e-9"
+    sub = cc.pack([cases[i] for i in idx])
+    g = ctx.classic_turns(sub, out=cc.sentinel_results(sub))
+    assert np.array_equal(g.status[:size], first.status[idx]) and np.array_equal(g.n_path[:size], first.n_path[idx])
+    assert np.array_equal(_bits(g.path[:size]), _bits(first.path[idx]))
+    assert g.status[size] == cc.ISENTINEL and np.all(g.path[size] == cc.SENTINEL)
+
+
+def test_scratch_growth(first):
+    """A fresh context: the batch with 200 samples a turn, then with 512 (ctx->ct_ws grows), then with 200 again.
+    Every good turn has fewer than 200 samples, so all three agree with the first launch."""
+    cases, pk, host = _edge_case()
+    fresh = _native.Context(0)
+    B = pk.batch
+    for cap in (200, 512, 200):
+        p = cc.pack(cases, cap_samples=cap)
+        g = fresh.classic_turns(p, out=cc.sentinel_results(p))
+        assert np.array_equal(g.status, first.status) and np.array_equal(g.n_path, first.n_path), cap
+        for b, c in enumerate(cases):
+            if c[3] != "overflow":
+                assert np.array_equal(_bits(g.path[b]), _bits(first.path[b])), (cap, b, c[0])
+    assert (host.status[:B] == 0).sum() == 6       # the four good turns and the two wide-row turns
+
+
+def test_device_entry_equals_the_staged_entry(ctx, first):
+    """htp_classic_turn_batch_device on torch-resident buffers on a side stream: the staged entry's outputs exactly,
+    sentinels and the turn of storage beyond the batch included."""
+    import torch
+    _, pk, _ = _edge_case()
+    dev = torch.device("cuda", 0)
+    t_in = {k: torch.from_numpy(getattr(pk, k)).to(dev) for k in ("params", "desc", "poly_off", "vertices")}
+    pre = cc.sentinel_results(pk)
+    t_out = {k: torch.from_numpy(getattr(pre, k)).to(dev) for k in ("status", "n_path", "path")}
+    stream = torch.cuda.Stream(dev)
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    ctx.classic_turns_device(pk, {k: v.data_ptr() for k, v in t_in.items()}, {k: v.data_ptr() for k, v in t_out.items()},
+                             stream=stream.cuda_stream)
+    stream.synchronize()
+    for k in ("status", "n_path", "path"):
+        assert np.array_equal(_bits(t_out[k].cpu().numpy()), _bits(getattr(first, k))), k
+    assert ctx.classic_last_ms() > 0.0
+    del t_in
+
+
+def test_api_errors_reach_the_caller(ctx):
+    cases = cc.good_cases()
+    with pytest.raises(RuntimeError, match="classic: bad sizes"):
+        ctx.classic_turns(cc.pack(cases, cap_samples=8))
+    with pytest.raises(RuntimeError, match="classic: bad sizes"):
+        ctx.classic_turns(cc.pack(cases, cap_path=0))
+    pk = cc.pack(cases)
+    pk.desc[1, 0] = len(pk.poly_off) - 1          # a body polygon id one past the pool
+    with pytest.raises(RuntimeError, match="classic: polygon ids out of range"):
+        ctx.classic_turns(pk)
+    pk = cc.pack(cases)
+    pk.poly_off[-1] += 1                          # poly_off[npoly] != nvert
+    with pytest.raises(RuntimeError, match="classic: poly_off"):
+        ctx.classic_turns(pk)
+    empty = cc.pack([])
+    r = ctx.classic_turns(empty, out=cc.sentinel_results(empty))      # batch = 0 returns at once
+    assert r.status[0] == cc.ISENTINEL and np.all(r.path == cc.SENTINEL)
+
+
+def test_sample_kernel_with_a_tiny_step(ctx):
+    """One launch of the sampled pose search with the circle-back turn of step 1e-9 between good turns: the host
+    build's statuses (every candidate of that turn C_OVERFLOW), the good turns' winners unchanged."""
+    import _sample_host as sh
+    turns = cc.sample_turns()
+    pk = _native.SamplePacked(turns, cap_samples=cc.SAMPLE_CAP)
+    host = sh.sample_host(pk)
+    dev = ctx.classic_sample(pk)
+    assert host.status.tolist() == [_native.SMP_OK, _native.SMP_OVERFLOW, _native.SMP_OK]
+    assert np.array_equal(dev.status, host.status) and np.array_equal(dev.cand_status, host.cand_status)
+    assert np.array_equal(dev.winner, host.winner) and np.array_equal(dev.n_feasible, host.n_feasible)
+    fin = np.isfinite(host.cand_score)
+    assert np.array_equal(np.isfinite(dev.cand_score), fin)
+    assert np.all(np.abs(dev.cand_score[fin] - host.cand_score[fin]) <= 1e-10)      # tests/test_gpu_sample.py's bound
+    good = ctx.classic_sample(_native.SamplePacked([turns[0], turns[2]], cap_samples=cc.SAMPLE_CAP))
+    assert np.array_equal(good.winner, dev.winner[[0, 2]]) and np.array_equal(good.score, dev.score[[0, 2]])

@@ -40,6 +40,23 @@ def test_hastar_kernel_keeps_two_wavefronts_per_simd(ks):
     assert r["private_segment_fixed_size"] <= 528, r       # 1 040 B/lane before the round-6 lane-coverage rewrite
 
 
+@pytest.mark.parametrize("part,vgpr,scratch", [
+    # the build before the planner's sample counts were guarded (classic_core.h arc_new / offset_pose, classic_batch.h):
+    # classic_kernel 254 VGPRs (6 of them AGPRs), 592 B scratch; classic_sample_kernel<5> (Dubins / circle-back)
+    # 185 VGPRs, no scratch; classic_sample_kernel<2> (Reeds-Shepp) 278 VGPRs (22 AGPRs), 208 B scratch.  No scratch
+    # growth; VGPRs up to the occupancy step the kernel stands on (256: two wavefronts per SIMD, 512: one), as above.
+    ("classic_kernelE", 256, 592),
+    ("k_classicE", 256, 592),              # the same planner as the chain's first stage: the same numbers
+    ("classic_sample_kernelILi5E", 256, 0),
+    ("classic_sample_kernelILi2E", 512, 208),
+])
+def test_classic_and_sample_kernels_keep_their_budgets(ks, part, vgpr, scratch):
+    r = _one(ks, part)
+    assert r["vgpr_count"] <= vgpr, r
+    assert r["vgpr_spill_count"] == 0, r
+    assert r["private_segment_fixed_size"] <= scratch, r
+
+
 def test_every_kernel_has_metadata(ks):
     names = " ".join(ks)
     for part in ("obca_solve_kernel", "hastar_kernel", "rs_", "ypark", "oge", "classic", "refpath"):
