@@ -708,7 +708,8 @@ EXPORTS = ["htp_obca_sizes", "htp_create", "htp_destroy", "htp_last_error", "htp
            "htp_obca_track_batch", "htp_obca_track_batch_device", "htp_obca_track_last_ms",
            "htp_obca_lqr_batch", "htp_obca_lqr_batch_device", "htp_obca_lqr_last_ms",
            "htp_obca_ltrack_batch", "htp_obca_ltrack_batch_device", "htp_obca_ltrack_last_ms",
-           "htp_classic_sample_batch", "htp_classic_sample_batch_device", "htp_classic_sample_last_ms"]
+           "htp_classic_sample_batch", "htp_classic_sample_batch_device", "htp_classic_sample_last_ms",
+           "htp_speed_profile_batch", "htp_speed_profile_batch_device", "htp_speed_profile_last_ms"]
 
 
 def _declare(lib):
@@ -882,6 +883,13 @@ def _declare(lib):
     lib.htp_classic_sample_batch_device.restype = ctypes.c_int
     lib.htp_classic_sample_last_ms.argtypes = [ctypes.c_void_p]
     lib.htp_classic_sample_last_ms.restype = ctypes.c_double
+    lib.htp_speed_profile_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(SpdIn), ctypes.POINTER(SpdResult)]
+    lib.htp_speed_profile_batch.restype = ctypes.c_int
+    lib.htp_speed_profile_batch_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(SpdIn), ctypes.POINTER(SpdResult),
+                                                   ctypes.c_void_p]
+    lib.htp_speed_profile_batch_device.restype = ctypes.c_int
+    lib.htp_speed_profile_last_ms.argtypes = [ctypes.c_void_p]
+    lib.htp_speed_profile_last_ms.restype = ctypes.c_double
     if hasattr(lib, "htp_bk_probe"):   # likewise
         lib.htp_bk_probe.argtypes = [ctypes.c_void_p] + BK_PROBE_ARGS + [ctypes.c_void_p]
         lib.htp_bk_probe.restype = ctypes.c_int
@@ -1657,6 +1665,119 @@ class SampleResults:
                          g("cand_status"))
 
 
+# ------------------------------------------------------------ speed profile of planner paths (htp_speed.hip)
+SPD_NLIM, SPD_NNODE, SPD_NKIND, SPD_NSUM = 10, 7, 7, 16
+SPD_OK, SPD_SKIPPED, SPD_BAD_INPUT = 0, 1, 2
+SPD_STATUS = {0: "ok", 1: "skipped", 2: "bad_input"}
+SPD_LIMITS = ("wheel_base", "v_fwd", "v_rev", "acc", "dec", "a_lat", "steer_rate", "max_steer", "v0", "v1")
+SPD_NODE_COLUMNS = ("S", "t", "v", "accel", "steer", "steer_rate", "cap")
+SPD_KINDS = ("stop", "vmax", "alat", "steer_rate", "endpoint", "acc", "dec")
+SPD_SUMMARY = ("T", "length", "len_fwd", "len_rev", "stops", "dwell", "peak_v", "peak_lat", "max_steer") + tuple(
+    "time_" + k for k in SPD_KINDS)
+SPD_FLAGS = {"HOP": 1, "STEER_EXCEEDS": 2, "TRUNCATED": 4, "BAD_TIME": 8}
+
+
+class SpdIn(ctypes.Structure):  # htp_speed_in
+    _fields_ = [("batch", ctypes.c_int32), ("cap_path", ctypes.c_int32), ("path", ctypes.c_void_p),
+                ("n_path", ctypes.c_void_p), ("path_status", ctypes.c_void_p), ("limits", ctypes.c_void_p),
+                ("dt", ctypes.c_double), ("cap_rows", ctypes.c_int32), ("max_groups", ctypes.c_int32)]
+
+
+class SpdResult(ctypes.Structure):  # htp_speed_result
+    _fields_ = [("status", ctypes.c_void_p), ("flags", ctypes.c_void_p), ("summary", ctypes.c_void_p),
+                ("node", ctypes.c_void_p), ("active", ctypes.c_void_p), ("count", ctypes.c_void_p),
+                ("rows", ctypes.c_void_p), ("stage", ctypes.c_void_p)]
+
+
+class SpeedPacked:
+    """Paths for htp_speed_profile_batch.  paths: a list of [n][5] arrays (x, y, yaw, k, dir), or a ClassicResults whose
+    path / n_path / status are taken as they are; limits: one row of SPD_LIMITS per path (or one for all);
+    status: optional per-path planner status (non-zero: skipped); dt = 0: no fixed-period rows; cap_rows defaults to
+    4096 when dt > 0; max_groups = 0 lets the library choose the workgroup count."""
+
+    def __init__(self, paths, limits, cap_path=None, dt=0.0, cap_rows=None, status=None, max_groups=0):
+        if isinstance(paths, ClassicResults):
+            self.path, self.n_path = paths.path, paths.n_path
+            status = paths.status if status is None else status
+        else:
+            arrs = [np.asarray(p, dtype=np.float64).reshape(-1, 5) for p in paths]
+            cap = int(cap_path) if cap_path is not None else max([len(a) for a in arrs] + [2])
+            self.path = np.zeros((len(arrs), cap, 5))
+            self.n_path = np.array([len(a) for a in arrs], np.int32).reshape(len(arrs))
+            for b, a in enumerate(arrs):
+                self.path[b, :min(len(a), cap)] = a[:cap]
+        self.batch, self.cap_path = self.path.shape[0], self.path.shape[1]
+        lim = np.asarray(limits, dtype=np.float64)
+        self.limits = np.ascontiguousarray(np.broadcast_to(lim.reshape(-1, SPD_NLIM), (self.batch, SPD_NLIM)))
+        self.path_status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(self.batch)
+        self.dt, self.max_groups = float(dt), int(max_groups)
+        self.cap_rows = int(cap_rows) if cap_rows is not None else (4096 if self.dt > 0.0 else 0)
+
+    @classmethod
+    def resident(cls, batch, cap_path, limits, dt=0.0, cap_rows=None, max_groups=0):
+        """The description of `batch` paths of `cap_path` rows that live on the device already (say, the buffers
+        htp_classic_turn_batch_device filled): sizes, options and the host copy of the limits, no path arrays.  For
+        Context.speed_profile_device only, which takes path / n_path / limits (and path_status) as device pointers."""
+        self = cls.__new__(cls)
+        self.batch, self.cap_path = int(batch), int(cap_path)
+        self.path = self.n_path = self.path_status = None
+        lim = np.asarray(limits, dtype=np.float64)
+        self.limits = np.ascontiguousarray(np.broadcast_to(lim.reshape(-1, SPD_NLIM), (self.batch, SPD_NLIM)))
+        self.dt, self.max_groups = float(dt), int(max_groups)
+        self.cap_rows = int(cap_rows) if cap_rows is not None else (4096 if self.dt > 0.0 else 0)
+        return self
+
+    def struct(self, ptrs=None):
+        p = ptrs or {}
+
+        def g(name):
+            a = getattr(self, name)
+            return p.get(name, None if a is None else a.ctypes.data)
+        return SpdIn(self.batch, self.cap_path, g("path"), g("n_path"), g("path_status"), g("limits"), self.dt,
+                     self.cap_rows, self.max_groups)
+
+
+class SpeedResults:
+    """status [B] (SPD_*), flags [B] (SPD_FLAGS bits), summary [B, 16] (SPD_SUMMARY), count [B]; with nodes=True node
+    [B, cap_path, 7] (SPD_NODE_COLUMNS) and active [B, cap_path] (index into SPD_KINDS); with dt > 0 rows
+    [B, cap_rows, 10] (TIMELINE_COLUMNS) and stage.  `fill` pre-fills the doubles (ints: -77), so what the kernel leaves
+    unwritten can be told."""
+
+    def __init__(self, packed, nodes=True, stage=True, fill=0.0):
+        B, cap, capr = packed.batch, packed.cap_path, packed.cap_rows
+        ifill = 0 if fill == 0.0 else -77
+        self.cap_rows = capr
+        self.status = np.full(B, ifill, np.int32)
+        self.flags = np.full(B, ifill, np.int32)
+        self.summary = np.full((B, SPD_NSUM), fill)
+        self.count = np.full(B, ifill, np.int32)
+        self.node = np.full((B, cap, SPD_NNODE), fill) if nodes else None
+        self.active = np.full((B, cap), ifill, np.int32) if nodes else None
+        self.rows = np.full((B, capr, len(TIMELINE_COLUMNS)), fill) if packed.dt > 0.0 else None
+        self.stage = np.full((B, capr), ifill, np.int32) if packed.dt > 0.0 and stage else None
+
+    def struct(self, ptrs=None):
+        p = ptrs or {}
+
+        def g(name):
+            a = getattr(self, name)
+            return p.get(name, None if a is None else a.ctypes.data)
+        return SpdResult(g("status"), g("flags"), g("summary"), g("node"), g("active"), g("count"), g("rows"),
+                         g("stage"))
+
+    def flag_names(self, k):
+        return [n for n, bit in SPD_FLAGS.items() if int(self.flags[k]) & bit]
+
+    def timeline(self, k):
+        """The written fixed-period rows of path k."""
+        return self.rows[k, :min(int(self.count[k]), self.cap_rows)].copy()
+
+    def as_dict(self, k):
+        d = {"status": SPD_STATUS[int(self.status[k])], "flags": self.flag_names(k), "count": int(self.count[k])}
+        d.update({n: float(self.summary[k, j]) for j, n in enumerate(SPD_SUMMARY)})
+        return d
+
+
 class ChainBatch(ctypes.Structure):  # htp_chain_batch
     _fields_ = [("batch", ctypes.c_int32), ("N", ctypes.c_int32), ("M", ctypes.c_int32),
                 ("scenes", OgeBatch), ("turns", CtBatch), ("margin", ctypes.c_void_p),
@@ -1843,6 +1964,33 @@ class Context:
 
     def classic_sample_last_ms(self):
         return self.lib.htp_classic_sample_last_ms(self.ctx)
+
+    def speed_profile(self, packed, nodes=True, stage=True, out=None):
+        """Batched speed profile and timed trajectory of planner paths (host buffers) -> SpeedResults.  `out`: a
+        SpeedResults to fill; what the kernel leaves unwritten stays as it was."""
+        r = SpeedResults(packed, nodes, stage) if out is None else out
+        b, rs = packed.struct(), r.struct()
+        if self.lib.htp_speed_profile_batch(self.ctx, ctypes.byref(b), ctypes.byref(rs)) != 0:
+            raise RuntimeError(f"[htp] htp_speed_profile_batch failed: {self.error()}")
+        return r
+
+    def speed_profile_device(self, packed, dev_ptrs, out_ptrs, stream=None):
+        """Device-resident speed profile on `stream`, not synchronised.  dev_ptrs: device pointers of path, n_path,
+        limits and optionally path_status (e.g. the buffers htp_classic_turn_batch_device filled on the same stream);
+        out_ptrs: those of the SpeedResults arrays (node, active, rows, stage optional)."""
+        for k in ("path", "n_path", "limits"):
+            if k not in dev_ptrs:
+                raise KeyError(f"[htp] speed_profile_device: the device pointer of {k!r} is missing")
+        b, r = packed.struct(dev_ptrs), SpdResult()
+        if "path_status" not in dev_ptrs:
+            b.path_status = None
+        for k, v in out_ptrs.items():
+            setattr(r, k, v)
+        if self.lib.htp_speed_profile_batch_device(self.ctx, ctypes.byref(b), ctypes.byref(r), stream) != 0:
+            raise RuntimeError(f"[htp] htp_speed_profile_batch_device failed: {self.error()}")
+
+    def speed_profile_last_ms(self):
+        return self.lib.htp_speed_profile_last_ms(self.ctx)
 
     def oge_obstacles(self, packed, halfspaces=True):
         """Batched orchard scene -> OBCA obstacle polygons (+ halfspaces), host buffers -> OgeResults."""

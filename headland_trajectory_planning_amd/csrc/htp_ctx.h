@@ -100,6 +100,10 @@ struct htp_ctx {
   htp_event_pair sample_ev;
   htp_device_buffer sample_ws, sample_tab;
   int sample_groups = 0;   // workgroups of the candidate kernel resident at once (0: not yet asked)
+  // speed profile (htp_speed.hip): per-workgroup node scratch
+  htp_event_pair speed_ev;
+  htp_device_buffer speed_ws;
+  int speed_groups = 0;    // workgroups of the kernel resident at once (0: not yet asked)
 };
 
 static inline int fail(htp_ctx* c, const std::string& m) {
@@ -117,6 +121,17 @@ static inline int fail(htp_ctx* c, const std::string& m) {
 // (`done` = that launch's end event): stream order when both are on one stream, an event wait otherwise.
 static inline int order_after(htp_ctx* ctx, hipEvent_t done, hipStream_t s) {
   if (done && hipEventQuery(done) == hipErrorNotReady) HIPCHK(hipStreamWaitEvent(s, done, 0));
+  return 0;
+}
+
+// A context buffer grown to `need` bytes (its contents are not kept).
+static inline int ensure_buffer(htp_ctx* ctx, htp_device_buffer& buf, size_t need) {
+  if (buf.bytes >= need) return 0;
+  if (buf.p) (void)hipFree(buf.p);
+  buf.p = nullptr;
+  buf.bytes = 0;
+  HIPCHK(hipMalloc(&buf.p, need));
+  buf.bytes = need;
   return 0;
 }
 

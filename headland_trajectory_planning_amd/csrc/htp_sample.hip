@@ -53,16 +53,6 @@ __global__ __launch_bounds__(64) void classic_sample_winner_kernel(htp_classic_s
   smp::run_winner(c, in, out, cand_score, cand_status, b);
 }
 
-int ensure_buffer(htp_ctx* ctx, htp_device_buffer& buf, size_t need) {
-  if (buf.bytes >= need) return 0;
-  if (buf.p) (void)hipFree(buf.p);
-  buf.p = nullptr;
-  buf.bytes = 0;
-  HIPCHK(hipMalloc(&buf.p, need));
-  buf.bytes = need;
-  return 0;
-}
-
 int enqueue(htp_ctx* ctx, const htp_classic_sample_in& in, const htp_classic_sample_result& out, hipStream_t s) {
   if (!ctx->sample_ev.e0) HIPCHK(hipEventCreate(&ctx->sample_ev.e0));
   if (!ctx->sample_ev.e1) HIPCHK(hipEventCreate(&ctx->sample_ev.e1));

@@ -434,3 +434,184 @@ def sample_start_end_pose_batch(requests, device=None, **opts):
             raise RuntimeError("[htp] sampled pose search: turn %d ended %s" % (k, _native.SMP_STATUS[st]))
         out.append(sample_result_tuple(t, st, res.poses[k]))
     return out
+
+
+# ------------------------------------------------------------------ speed profile and timed trajectory of a path
+SPEED_KINDS = ("stop", "vmax", "alat", "steer_rate", "endpoint", "acc", "dec")
+SPEED_LIMIT_DEFAULTS = dict(v_fwd=1.0, v_rev=1.0, acc=1.0, dec=1.0, a_lat=0.0, steer_rate=0.7, v0=0.0, v1=0.0)
+
+
+def speed_limits(car, **limits):
+    """The limits row of one path (include/htp.h HTP_SPD_L_*): wheelbase and max_steer from the car, the rest from
+    `limits` over synth's values (max_velocity 1, max_accel 1, max_steer_rate 0.7), so a classic turn and an OBCA turn
+    are timed under the same limits.  wheel_base / max_steer in `limits` override the car's."""
+    for k in limits:
+        if k not in SPEED_LIMIT_DEFAULTS and k not in ("wheel_base", "max_steer"):
+            raise TypeError("speed_profile: unknown limit %r" % (k,))
+    m = dict(SPEED_LIMIT_DEFAULTS, **limits)
+    wb = m.get("wheel_base", getattr(car, "WHEEL_BASE", None))
+    ms = m.get("max_steer", getattr(car, "MAX_STEER", None))
+    return np.array([wb, m["v_fwd"], m["v_rev"], m["acc"], m["dec"], m["a_lat"], m["steer_rate"], ms, m["v0"],
+                     m["v1"]], dtype=np.float64)
+
+
+def _speed_interval(wi, wj, ds, dd, acc, dec, omega):
+    """(dt, a, kind, t1, vm) of one interval; kind 0 ramp, 1 dwell, 2 hop."""
+    vi, vj = math.sqrt(wi), math.sqrt(wj)
+    if ds == 0.0:
+        return (abs(dd) / omega if omega > 0.0 and dd != 0.0 else 0.0), 0.0, 1, 0.0, 0.0
+    if vi + vj > 0.0:
+        return 2.0 * ds / (vi + vj), (wj - wi) / (2.0 * ds), 0, 0.0, 0.0
+    vm = math.sqrt(2.0 * acc * dec * ds / (acc + dec))
+    t1 = vm / acc
+    return t1 + vm / dec, acc, 2, t1, vm
+
+
+def speed_profile(path, car, dt=0.0, cap_rows=None, libm=None, **limits):
+    """The maximal speed profile of one path (rows x, y, yaw, k, dir) as include/htp.h defines it, in plain numpy with
+    sequential recurrences: the statement the batched kernel is tested against.  Returns a dict: status ("ok" /
+    "bad_input"), S, t, v (signed), accel, steer, steer_rate, cap, w, active [n], T, length, len_fwd, len_rev, stops,
+    stop_nodes, dwell, peak_v, peak_lat, max_steer, time_kind [7], flags (set of "hop", "steer_exceeds", "truncated",
+    "bad_time"), count and, with dt > 0, rows [min(count, cap_rows)][10] and stage.  `libm`: an object with atan and
+    hypot (default: math); the tests pass the project's correctly rounded ones, which the kernel uses."""
+    lm = math if libm is None else libm
+    lim = speed_limits(car, **limits)
+    L, vf, vr, acc, dec, alat, omega, max_steer, v0, v1 = [float(x) for x in lim]
+    P = np.asarray(path, dtype=np.float64)
+    bad = P.ndim != 2 or P.shape[0] < 2 or P.shape[1] < 5 or not np.all(np.isfinite(lim))
+    bad = bad or not np.all(np.isfinite(P[:, :5])) or not np.all(np.abs(P[:, 4]) == 1.0)
+    bad = bad or not (L > 0 and vf > 0 and vr > 0 and acc > 0 and dec > 0) or alat < 0 or omega < 0 or v0 < 0 or v1 < 0
+    if bad:
+        return dict(status="bad_input", count=0, flags=set())
+    n = len(P)
+    x, y, yaw, k, d = P[:, 0], P[:, 1], P[:, 2], P[:, 3], P[:, 4]
+    ds = np.array([lm.hypot(x[i + 1] - x[i], y[i + 1] - y[i]) for i in range(n - 1)])
+    S = np.concatenate([[0.0], np.cumsum(ds)])
+    dl = np.array([lm.atan(L * k[i]) for i in range(n)])
+    ddl = dl[1:] - dl[:-1]
+    stop = np.zeros(n, bool)
+    stop[:-1] = d[1:] != d[:-1]
+    inf = math.inf
+    c = np.zeros(n)
+    kind = np.zeros(n, np.int32)
+    for i in range(n):
+        vmax, sr, endp = inf, inf, inf
+        if i > 0:
+            vmax = vf if d[i] > 0 else vr
+            if omega > 0.0 and ddl[i - 1] != 0.0:
+                sr = omega * ds[i - 1] / abs(ddl[i - 1])
+        if i < n - 1:
+            vmax = min(vmax, vf if d[i + 1] > 0 else vr)
+            if omega > 0.0 and ddl[i] != 0.0:
+                sr = min(sr, omega * ds[i] / abs(ddl[i]))
+        al = math.sqrt(alat / abs(k[i])) if alat > 0.0 and k[i] != 0.0 else inf
+        if i == 0:
+            endp = v0
+        if i == n - 1:
+            endp = min(endp, v1)
+        cands = [0.0 if stop[i] else inf, vmax, al, sr, endp]
+        c[i] = min(cands)
+        kind[i] = cands.index(c[i])
+    c2 = c * c
+    f = np.zeros(n)
+    fb = np.full(n, inf)           # the forward bound of node i
+    f[0] = c2[0]
+    for i in range(n - 1):
+        fb[i + 1] = f[i] + 2.0 * acc * ds[i]
+        f[i + 1] = min(c2[i + 1], fb[i + 1])
+    w = f.copy()
+    bb = np.full(n, inf)           # the backward bound
+    for i in range(n - 2, -1, -1):
+        bb[i] = w[i + 1] + 2.0 * dec * ds[i]
+        w[i] = min(f[i], bb[i])
+    active = np.where(w == c2, kind, np.where(fb < bb, 5, 6)).astype(np.int32)
+    iv = [_speed_interval(w[i], w[i + 1], ds[i], ddl[i], acc, dec, omega) for i in range(n - 1)]
+    dts = np.array([q[0] for q in iv])
+    t = np.concatenate([[0.0], np.cumsum(dts)])
+    T = float(t[-1])
+    g = np.concatenate([d[1:], d[-1:]])
+    v = np.sqrt(w)
+    a = np.array([q[1] for q in iv] + [0.0])
+    rate = np.array([ddl[i] / dts[i] if dts[i] > 0.0 else 0.0 for i in range(n - 1)] + [0.0])
+    len_f = len_r = dwell = 0.0
+    tk = [0.0] * len(SPEED_KINDS)
+    for i in range(n - 1):
+        if d[i + 1] > 0:
+            len_f += ds[i]
+        else:
+            len_r += ds[i]
+        if iv[i][2] == 1:
+            dwell += dts[i]
+        tk[active[i]] += dts[i]
+    hops = [q[4] for q in iv if q[2] == 2]
+    flags = set()
+    if hops:
+        flags.add("hop")
+    if np.max(np.abs(dl)) > max_steer:
+        flags.add("steer_exceeds")
+    out = dict(status="ok", S=S, t=t, v=g * v, accel=g * a, steer=dl, steer_rate=rate, cap=c, w=w, active=active,
+               T=T, length=float(S[-1]), len_fwd=len_f, len_rev=len_r, stops=int(stop.sum()),
+               stop_nodes=np.nonzero(stop)[0], dwell=dwell, peak_v=float(max([np.max(v)] + hops)),
+               peak_lat=float(np.max(w * np.abs(k))), max_steer=float(np.max(np.abs(dl))), time_kind=np.array(tk),
+               flags=flags, count=0)
+    if dt > 0.0:
+        quot = T / dt
+        if not quot < 2.0 ** 30:
+            flags.add("bad_time")
+            return out
+        nr = int(quot)
+        while nr > 0 and (nr - 1) * dt >= T:
+            nr -= 1
+        while nr * dt < T:
+            nr += 1
+        out["count"] = nr + 1
+        cap_rows = nr + 1 if cap_rows is None else int(cap_rows)
+        if nr + 1 > cap_rows:
+            flags.add("truncated")
+        rows, stage = [], []
+        for r in range(min(nr + 1, cap_rows)):
+            if r == nr:
+                q = iv[n - 2]
+                rows.append([T, x[-1], y[-1], d[-1] * v[-1], yaw[-1], dl[-1], d[-1] * (-dec if q[2] == 2 else q[1]),
+                             rate[n - 2], k[-1], S[-1]])
+                stage.append(n - 1)
+                continue
+            s = r * dt
+            i = int(np.searchsorted(t[:n - 1], s, side="right")) - 1
+            dti, ai, kd, t1, vm = iv[i]
+            tau = s - t[i]
+            dist = vel = ac = 0.0
+            if kd == 1:
+                lam = tau / dti
+            else:
+                if kd == 0:
+                    dist = v[i] * tau + 0.5 * ai * tau * tau
+                    vel, ac = v[i] + ai * tau, ai
+                elif tau < t1:
+                    dist, vel, ac = 0.5 * acc * tau * tau, acc * tau, acc
+                else:
+                    t2 = tau - t1
+                    dist = 0.5 * acc * t1 * t1 + vm * t2 - 0.5 * dec * t2 * t2
+                    vel, ac = vm - dec * t2, -dec
+                lam = dist / ds[i]
+            lam = min(max(lam, 0.0), 1.0)
+            dy = yaw[i + 1] - yaw[i]
+            kk = k[i] + lam * (k[i + 1] - k[i])
+            rows.append([s, x[i] + lam * (x[i + 1] - x[i]), y[i] + lam * (y[i + 1] - y[i]), d[i + 1] * vel,
+                         yaw[i] + lam * (dy - 2.0 * math.pi * math.floor((dy + math.pi) / (2.0 * math.pi))),
+                         lm.atan(L * kk), d[i + 1] * ac, rate[i], kk, S[i] + dist])
+            stage.append(i)
+        out["rows"] = np.array(rows).reshape(-1, 10)
+        out["stage"] = np.array(stage, np.int32)
+    return out
+
+
+def speed_profile_batch(paths, car, device=None, dt=0.0, cap_rows=None, status=None, **limits):
+    """The speed profile of many paths in one launch (htp_speed_profile_batch) -> _native.SpeedResults.  `paths`: a list
+    of [n][5] arrays; `status`: optional per-path planner status, non-zero paths are skipped; `limits` as
+    speed_profile (one set for the batch).  `device`: a _native.Context, a device index, or None for device 0."""
+    from .. import _native
+    ctx = device if isinstance(device, _native.Context) else _native.Context(0 if device is None else int(device))
+    packed = _native.SpeedPacked(paths, [speed_limits(car, **limits)] * len(paths), dt=dt, cap_rows=cap_rows,
+                                 status=status)
+    return ctx.speed_profile(packed)

@@ -1148,6 +1148,107 @@ int htp_classic_sample_batch_device(htp_ctx* ctx, const htp_classic_sample_in* i
 double htp_classic_sample_last_ms(htp_ctx* ctx);   /* candidate kernels + winner kernel of the last launch */
 
 /* ---------------------------------------------------------------------------
+ * Maximal speed profile and timed trajectory of planner paths (no reference counterpart: the only speed a classic
+ * turn gets there is get_init_ref_path's v = +-desired_v, R/obca_py/util.py:62-113; csrc/speed_core.h, DESIGN.md
+ * s.3.17).  One wavefront per path, workgroups stride over the batch.
+ *
+ * Input per path: rows [n][5] = x, y, yaw, k, dir (dir = +-1), the layout of htp_classic_result.path, and a limits row
+ *   (HTP_SPD_L_*).  A non-zero path_status entry ends the path HTP_SPD_SKIPPED, so htp_classic_result.status can be
+ *   passed straight in.
+ * Geometry.  ds_i = hypot(x_{i+1} - x_i, y_{i+1} - y_i); S_0 = 0, S_{i+1} = S_i + ds_i, a serial left-to-right sum (as
+ *   refpath_core.h and the timeline's A_i); delta_i = atan(L k_i).  Interval i runs from node i to node i+1 in gear
+ *   g_i = dir_{i+1}.  Node i is a STOP NODE when dir_{i+1} != dir_i: that row is the cusp itself (the Reeds-Shepp sampler
+ *   writes the junction with the finishing segment's direction), the gap to the next row is driven in the new gear.
+ * Node cap c_i = the least of
+ *   VMAX        v_fwd or v_rev of each adjacent interval (by its gear);
+ *   ALAT        sqrt(a_lat / |k_i|) when a_lat > 0 and k_i != 0;
+ *   STEER_RATE  omega ds_j / |ddelta_j| for each adjacent interval j with ddelta_j = delta_{j+1} - delta_j != 0, when
+ *               omega > 0.  The cap holds at BOTH ends of the interval, so the interval's mean speed is at most the cap
+ *               and its steering rate at most omega; it is conservative by up to 2x (an interval entered from rest could
+ *               leave at twice the cap).  This is what makes the curvature jumps of Dubins and Reeds-Shepp words
+ *               drivable.  A zero-length interval with a steer jump caps both its nodes at exactly 0;
+ *   STOP        0 at a stop node;
+ *   ENDPOINT    c_0 <- min(c_0, v0), c_{n-1} <- min(c_{n-1}, v1).
+ * Profile, with w = v^2: f_0 = c_0^2, f_{i+1} = min(c_{i+1}^2, f_i + 2 acc ds_i); w_{n-1} = f_{n-1},
+ *   w_i = min(f_i, w_{i+1} + 2 dec ds_i); v_i = sqrt(w_i): the largest profile under the caps and the two acceleration
+ *   bounds.  The library evaluates the two passes as min-plus scans, f_i = min(c_i^2, 2 acc S_i + min_{j<i}(c_j^2 -
+ *   2 acc S_j)) and its mirror image with dec; the node's own c_i^2 stays outside the shifted minimum, so a stop node is
+ *   exactly 0 and w_i == c_i^2 is decidable.  The scan form and the recurrence differ by rounding only.
+ * Interval time dt_i:
+ *   dwell  ds_i == 0: |ddelta_i| / omega (0 when omega is off or there is no jump);
+ *   else   2 ds_i / (v_i + v_{i+1}) when v_i + v_{i+1} > 0: constant acceleration a_i = (w_{i+1} - w_i) / (2 ds_i);
+ *   hop    both speeds 0 and ds_i > 0 (two cusps less than a step apart, or a two-row path): accelerate at acc to
+ *          w_m = 2 acc dec ds_i / (acc + dec), then brake at dec: dt_i = sqrt(w_m) / acc + sqrt(w_m) / dec; a_i is
+ *          reported as acc; the path gets HTP_SPD_F_HOP.
+ *   t_0 = 0, t_{i+1} = t_i + dt_i, a serial sum; T = t_{n-1}.
+ * Per-node outputs (nullable; rows from n_path on are left as they were): node[HTP_SPD_N_*] = S, t, signed speed g v,
+ *   signed acceleration g a_i and steering rate ddelta_i / dt_i of the LEAVING interval (g = g_i; the last node takes
+ *   g_{n-2}, acceleration 0 and rate 0; the rate of an interval with dt_i == 0 is 0), delta, cap c_i.
+ *   active (HTP_SPD_A_*): the cap's kind when w_i == c_i^2, the first in the order STOP, VMAX, ALAT, STEER_RATE,
+ *   ENDPOINT that attains the minimum; otherwise ACC when the forward bound is smaller than the backward one, else DEC.
+ * Summary per path (HTP_SPD_S_*): T, S_{n-1}, forward and reverse length, number of stop nodes, total dwell time, peak
+ *   speed, peak v^2 |k|, largest |delta_i|, and the time under each active kind (an interval's time is charged to its
+ *   entry node).  The sums are serial, in node order.  flags: HTP_SPD_F_*.
+ * Status.  HTP_SPD_BAD_INPUT: n_path < 2 or > cap_path; a non-finite double among those read (the path's rows and its
+ *   limits); a dir other than +-1; L, v_fwd, v_rev, acc or dec not positive; a_lat, omega, v0 or v1 negative.  Of a
+ *   HTP_SPD_SKIPPED or HTP_SPD_BAD_INPUT path only status (and count = 0, flags = 0) is written.
+ * Fixed-period rows (dt > 0), the columns and the row rule of htp_obca_timeline_batch: regular rows at s = k dt (a
+ *   product) while k dt < T, then exactly one final row, the last node at T (stage n-1, acceleration and steering rate
+ *   of the last interval).  count = rows needed; HTP_SPD_F_TRUNCATED when count > cap_rows (the first cap_rows rows are
+ *   written); T / dt >= 2^30 is HTP_SPD_F_BAD_TIME (count 0, no row).  The interval of a regular row is the largest i
+ *   with t_i <= s (it has dt_i > 0).  Within it tau = s - t_i; dist = v_i tau + a_i tau^2 / 2 (a hop uses its two
+ *   phases); lambda = dist / ds_i clamped to [0, 1] (a dwell: lambda = tau / dt_i, dist = 0); x, y and k are linear in
+ *   lambda; theta = yaw_i + lambda wrap(yaw_{i+1} - yaw_i), wrap(d) = d - 2 pi floor((d + pi) / (2 pi));
+ *   steer = atan(L k); arc = S_i + dist; v and accel are signed by g_i; steer_rate = ddelta_i / dt_i.
+ * Every loop is bounded by cap_path or cap_rows. */
+#define HTP_SPD_NLIM 10
+#define HTP_SPD_NNODE 7
+#define HTP_SPD_NKIND 7
+#define HTP_SPD_NSUM 16
+enum { HTP_SPD_L_WHEELBASE = 0, HTP_SPD_L_VFWD, HTP_SPD_L_VREV, HTP_SPD_L_ACC, HTP_SPD_L_DEC,
+       HTP_SPD_L_ALAT /* 0: off */, HTP_SPD_L_STEER_RATE /* 0: off */, HTP_SPD_L_MAXSTEER /* flag only */,
+       HTP_SPD_L_V0 /* entry speed */, HTP_SPD_L_V1 /* exit speed */ };
+enum { HTP_SPD_N_S = 0, HTP_SPD_N_T, HTP_SPD_N_V, HTP_SPD_N_ACC, HTP_SPD_N_STEER, HTP_SPD_N_STEER_RATE, HTP_SPD_N_CAP };
+enum { HTP_SPD_A_STOP = 0, HTP_SPD_A_VMAX, HTP_SPD_A_ALAT, HTP_SPD_A_STEER_RATE, HTP_SPD_A_ENDPOINT, HTP_SPD_A_ACC,
+       HTP_SPD_A_DEC };
+enum { HTP_SPD_S_T = 0, HTP_SPD_S_LENGTH, HTP_SPD_S_LEN_FWD, HTP_SPD_S_LEN_REV, HTP_SPD_S_STOPS, HTP_SPD_S_DWELL,
+       HTP_SPD_S_PEAK_V, HTP_SPD_S_PEAK_LAT, HTP_SPD_S_MAX_STEER, HTP_SPD_S_TIME_KIND /* .. + HTP_SPD_NKIND */ };
+enum { HTP_SPD_OK = 0, HTP_SPD_SKIPPED = 1, HTP_SPD_BAD_INPUT = 2 };
+enum { HTP_SPD_F_HOP = 1, HTP_SPD_F_STEER_EXCEEDS = 2 /* some |delta_i| > max_steer */, HTP_SPD_F_TRUNCATED = 4,
+       HTP_SPD_F_BAD_TIME = 8 };
+typedef struct {
+  int32_t batch, cap_path;
+  const double* path;          /* [batch][cap_path][5] x, y, yaw, k, dir */
+  const int32_t* n_path;       /* [batch] */
+  const int32_t* path_status;  /* nullable [batch]: non-zero -> HTP_SPD_SKIPPED */
+  const double* limits;        /* [batch][HTP_SPD_NLIM] */
+  double dt;                   /* output period; 0: no fixed-period rows */
+  int32_t cap_rows;            /* rows of storage per path (>= 2 when dt > 0) */
+  int32_t max_groups;          /* workgroups of the launch, each with 56 cap_path bytes of device scratch kept by the
+                                  context; 0: as many as are resident at once, but no more than fit 256 MiB */
+} htp_speed_in;
+typedef struct {
+  int32_t* status;             /* [batch] HTP_SPD_* */
+  int32_t* flags;              /* [batch] HTP_SPD_F_* bits */
+  double* summary;             /* [batch][HTP_SPD_NSUM] */
+  double* node;                /* nullable [batch][cap_path][HTP_SPD_NNODE] */
+  int32_t* active;             /* nullable [batch][cap_path] HTP_SPD_A_* */
+  int32_t* count;              /* [batch] fixed-period rows needed (0 when dt == 0) */
+  double* rows;                /* [batch][cap_rows][HTP_TIMELINE_NCOL]; required when dt > 0 */
+  int32_t* stage;              /* nullable [batch][cap_rows]: the interval of a regular row, n-1 for the final row */
+} htp_speed_result;
+/* API errors (-1 with a "[speed]" message, nothing launched): a null required argument, batch < 0, cap_path < 2, dt not
+ * finite or < 0, dt > 0 with cap_rows < 2 or without rows, max_groups < 0.  batch == 0 returns 0. */
+/* host pointers, synchronous; the caller's output arrays travel to the device and back, so what the kernel leaves
+ * unwritten stays as it was */
+int htp_speed_profile_batch(htp_ctx* ctx, const htp_speed_in* in, htp_speed_result* out);
+/* device pointers, enqueued on `stream`, not synchronised: behind htp_classic_turn_batch_device on the same stream it
+ * times that launch's path / n_path / status without a host round trip */
+int htp_speed_profile_batch_device(htp_ctx* ctx, const htp_speed_in* in, htp_speed_result* out, void* stream);
+/* duration (ms) of the last speed-profile kernel (hipEvents on its stream) */
+double htp_speed_profile_last_ms(htp_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * Orchard workload chain on the device (synth.make_orchard_instance's steps after the scene draws): for each
  * problem, the classic turn (htp_classic_turn_batch) -> get_init_ref_path at spacing ds / 2 = L / (2N - 2)
  * (ds = L / (N - 1), the resampled spacing), desired_v = min(ds / dT, 0.9) (R/obca_py/util.py:62-113) -> the init guess resampled to N rows and the
