@@ -709,7 +709,9 @@ EXPORTS = ["htp_obca_sizes", "htp_create", "htp_destroy", "htp_last_error", "htp
            "htp_obca_lqr_batch", "htp_obca_lqr_batch_device", "htp_obca_lqr_last_ms",
            "htp_obca_ltrack_batch", "htp_obca_ltrack_batch_device", "htp_obca_ltrack_last_ms",
            "htp_classic_sample_batch", "htp_classic_sample_batch_device", "htp_classic_sample_last_ms",
-           "htp_speed_profile_batch", "htp_speed_profile_batch_device", "htp_speed_profile_last_ms"]
+           "htp_speed_profile_batch", "htp_speed_profile_batch_device", "htp_speed_profile_last_ms",
+           "htp_pose_clearance_batch", "htp_pose_clearance_batch_device", "htp_pose_clearance_last_ms",
+           "htp_turn_select_batch", "htp_turn_select_batch_device", "htp_turn_select_last_ms"]
 
 
 def _declare(lib):
@@ -890,6 +892,20 @@ def _declare(lib):
     lib.htp_speed_profile_batch_device.restype = ctypes.c_int
     lib.htp_speed_profile_last_ms.argtypes = [ctypes.c_void_p]
     lib.htp_speed_profile_last_ms.restype = ctypes.c_double
+    lib.htp_pose_clearance_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(ClrIn), ctypes.POINTER(ClrResult)]
+    lib.htp_pose_clearance_batch.restype = ctypes.c_int
+    lib.htp_pose_clearance_batch_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(ClrIn), ctypes.POINTER(ClrResult),
+                                                    ctypes.c_void_p]
+    lib.htp_pose_clearance_batch_device.restype = ctypes.c_int
+    lib.htp_pose_clearance_last_ms.argtypes = [ctypes.c_void_p]
+    lib.htp_pose_clearance_last_ms.restype = ctypes.c_double
+    lib.htp_turn_select_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(SelIn), ctypes.POINTER(SelResult)]
+    lib.htp_turn_select_batch.restype = ctypes.c_int
+    lib.htp_turn_select_batch_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(SelIn), ctypes.POINTER(SelResult),
+                                                 ctypes.c_void_p]
+    lib.htp_turn_select_batch_device.restype = ctypes.c_int
+    lib.htp_turn_select_last_ms.argtypes = [ctypes.c_void_p]
+    lib.htp_turn_select_last_ms.restype = ctypes.c_double
     if hasattr(lib, "htp_bk_probe"):   # likewise
         lib.htp_bk_probe.argtypes = [ctypes.c_void_p] + BK_PROBE_ARGS + [ctypes.c_void_p]
         lib.htp_bk_probe.restype = ctypes.c_int
@@ -1778,6 +1794,207 @@ class SpeedResults:
         return d
 
 
+# ------------------------------------------------------------ pose clearance and turn selection (htp_clear.hip)
+CLR_NMETRIC, CLR_MAX_SUBSTEPS, SEL_MAX_CAND = 4, 16, 8
+CLR_OK, CLR_SKIPPED, CLR_BAD_INPUT, CLR_BAD_POLYTOPE = 0, 1, 2, 3
+CLR_STATUS = {0: "ok", 1: "skipped", 2: "bad_input", 3: "bad_polytope"}
+CLR_FLAGS = {"COLLISION": 1, "MARGIN": 2, "TRUNCATED": 4}
+CLR_METRICS = ("clearance", "clearance_node", "max_gap", "max_turn")
+SEL_VERDICT = {"NOT_PLANNED": 1, "BAD": 2, "SPEED_FLAG": 4, "CLEAR_FLAG": 8, "TOO_LONG": 16, "NONFINITE": 32}
+CLR_PATH_LAYOUT = dict(stride=5, cols=(0, 1, 2))        # planner paths x, y, yaw, k, dir
+CLR_TIMELINE_LAYOUT = dict(stride=10, cols=(1, 2, 4))   # fixed-period rows t, x, y, v, theta, ...
+CLR_SCENE_ARRAYS = ("obs_A", "obs_b", "body_G", "body_g")
+
+
+class ClrIn(ctypes.Structure):  # htp_clear_in
+    _fields_ = [("batch", ctypes.c_int32), ("cap_poses", ctypes.c_int32), ("stride", ctypes.c_int32),
+                ("col_x", ctypes.c_int32), ("col_y", ctypes.c_int32), ("col_yaw", ctypes.c_int32),
+                ("poses", ctypes.c_void_p), ("n_poses", ctypes.c_void_p), ("pose_status", ctypes.c_void_p),
+                ("scene", ctypes.c_void_p), ("n_scenes", ctypes.c_int32), ("M", ctypes.c_int32), ("K", ctypes.c_int32),
+                ("obs_edges", ctypes.c_void_p), ("body_edges", ctypes.c_void_p), ("obs_A", ctypes.c_void_p),
+                ("obs_b", ctypes.c_void_p), ("body_G", ctypes.c_void_p), ("body_g", ctypes.c_void_p),
+                ("margin", ctypes.c_void_p), ("substeps", ctypes.c_int32), ("margin_tol", ctypes.c_double),
+                ("max_groups", ctypes.c_int32)]
+
+
+class ClrResult(ctypes.Structure):  # htp_clear_result
+    _fields_ = [("status", ctypes.c_void_p), ("flags", ctypes.c_void_p), ("metrics", ctypes.c_void_p),
+                ("worst", ctypes.c_void_p), ("pose_clearance", ctypes.c_void_p)]
+
+
+class SelIn(ctypes.Structure):  # htp_select_in
+    _fields_ = [("batch", ctypes.c_int32), ("C", ctypes.c_int32), ("spd_status", ctypes.c_void_p),
+                ("spd_flags", ctypes.c_void_p), ("spd_summary", ctypes.c_void_p), ("rows", ctypes.c_void_p),
+                ("count", ctypes.c_void_p), ("cap_rows", ctypes.c_int32), ("clr_status", ctypes.c_void_p),
+                ("clr_flags", ctypes.c_void_p), ("clr_metrics", ctypes.c_void_p),
+                ("reject_speed_flags", ctypes.c_int32), ("reject_clear_flags", ctypes.c_int32),
+                ("t_max", ctypes.c_double)]
+
+
+class SelResult(ctypes.Structure):  # htp_select_result
+    _fields_ = [("verdict", ctypes.c_void_p), ("winner", ctypes.c_void_p), ("score", ctypes.c_void_p),
+                ("clearance", ctypes.c_void_p), ("out_rows", ctypes.c_void_p), ("out_count", ctypes.c_void_p)]
+
+
+def clear_scenes(scenes):
+    """A scenes dict for ClearPacked from a list of (obstacles, bodies), each a list of halfspace pairs (A [e, 2],
+    b [e]); every scene has the same edge counts."""
+    obs0, bod0 = scenes[0]
+    out = dict(obs_edges=np.array([len(b) for _, b in obs0], np.int32),
+               body_edges=np.array([len(b) for _, b in bod0], np.int32))
+    for name, which, part in (("obs_A", 0, 0), ("obs_b", 0, 1), ("body_G", 1, 0), ("body_g", 1, 1)):
+        out[name] = np.ascontiguousarray(np.stack(
+            [np.concatenate([np.asarray(h[part], dtype=np.float64) for h in sc[which]], axis=0) for sc in scenes]))
+    return out
+
+
+class ClearPacked:
+    """Pose sequences and scenes for htp_pose_clearance_batch.  poses: a list of [n][stride] arrays, or one
+    [B, cap, stride] array with n_poses; stride / cols: the layout (CLR_PATH_LAYOUT, CLR_TIMELINE_LAYOUT); scenes: a
+    PackedBatch or a dict with obs_edges, body_edges, obs_A [n_scenes, TEo, 2], obs_b, body_G, body_g (clear_scenes);
+    scene: per-path scene index (None: path p uses scene p); margin: None, a number or one per scene; status:
+    optional per-path status (non-zero: skipped)."""
+
+    def __init__(self, poses, scenes, scene=None, stride=5, cols=(0, 1, 2), n_poses=None, cap_poses=None, status=None,
+                 substeps=1, margin=None, margin_tol=0.0, max_groups=0):
+        self.stride, self.cols = int(stride), tuple(int(c) for c in cols)
+        if isinstance(poses, np.ndarray) and poses.ndim == 3:
+            self.poses = np.ascontiguousarray(poses, dtype=np.float64)
+            self.n_poses = np.ascontiguousarray(n_poses, dtype=np.int32).reshape(self.poses.shape[0])
+        else:
+            arrs = [np.asarray(p, dtype=np.float64).reshape(-1, self.stride) for p in poses]
+            cap = int(cap_poses) if cap_poses is not None else max([len(a) for a in arrs] + [1])
+            self.poses = np.zeros((len(arrs), cap, self.stride))
+            self.n_poses = np.array([len(a) for a in arrs], np.int32).reshape(len(arrs))
+            for b, a in enumerate(arrs):
+                self.poses[b, :min(len(a), cap)] = a[:cap]
+        self.batch, self.cap_poses = self.poses.shape[0], self.poses.shape[1]
+        self.pose_status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(self.batch)
+        self._options(scenes, scene, substeps, margin, margin_tol, max_groups)
+
+    def _options(self, scenes, scene, substeps, margin, margin_tol, max_groups):
+        get = scenes.get if isinstance(scenes, dict) else (lambda k: getattr(scenes, k))
+        self.obs_edges = np.ascontiguousarray(get("obs_edges"), dtype=np.int32)
+        self.body_edges = np.ascontiguousarray(get("body_edges"), dtype=np.int32)
+        for k in CLR_SCENE_ARRAYS:
+            setattr(self, k, None if get(k) is None else np.ascontiguousarray(get(k), dtype=np.float64))
+        self.M, self.K = len(self.obs_edges), len(self.body_edges)
+        if self.obs_b is not None:
+            self.n_scenes = int(self.obs_b.shape[0])
+        else:
+            self.n_scenes = int(get("n_scenes"))
+        self.scene = None if scene is None else np.ascontiguousarray(scene, dtype=np.int32).reshape(self.batch)
+        self.margin = None if margin is None else np.broadcast_to(
+            np.asarray(margin, dtype=np.float64).reshape(-1), (self.n_scenes,)).copy()
+        self.substeps, self.margin_tol, self.max_groups = int(substeps), float(margin_tol), int(max_groups)
+
+    @classmethod
+    def resident(cls, batch, cap_poses, edges, n_scenes, stride=5, cols=(0, 1, 2), substeps=1,
+                 margin_tol=0.0, max_groups=0):
+        """The description of `batch` sequences of `cap_poses` rows and `n_scenes` scenes that live on the device
+        already: sizes, layout and options, no arrays.  edges: (obs_edges, body_edges).  For
+        Context.pose_clearance_device only, which takes poses / n_poses / the scene arrays (and pose_status, scene,
+        margin) as device pointers."""
+        self = cls.__new__(cls)
+        self.batch, self.cap_poses = int(batch), int(cap_poses)
+        self.stride, self.cols = int(stride), tuple(int(c) for c in cols)
+        self.poses = self.n_poses = self.pose_status = None
+        self._options(dict(obs_edges=edges[0], body_edges=edges[1], obs_A=None, obs_b=None, body_G=None, body_g=None,
+                           n_scenes=n_scenes), None, substeps, None, margin_tol, max_groups)
+        return self
+
+    def struct(self, ptrs=None):
+        p = ptrs or {}
+
+        def g(name):
+            a = getattr(self, name)
+            return p.get(name, None if a is None else a.ctypes.data)
+        return ClrIn(self.batch, self.cap_poses, self.stride, self.cols[0], self.cols[1], self.cols[2], g("poses"),
+                     g("n_poses"), g("pose_status"), g("scene"), self.n_scenes, self.M, self.K,
+                     self.obs_edges.ctypes.data, self.body_edges.ctypes.data, g("obs_A"), g("obs_b"), g("body_G"),
+                     g("body_g"), g("margin"), self.substeps, self.margin_tol, self.max_groups)
+
+
+class ClearResults:
+    """status [B] (CLR_*), flags [B] (CLR_FLAGS bits), metrics [B, 4] (CLR_METRICS), worst [B, 4] (pose, substep,
+    obstacle, body); with poses=True pose_clearance [B, cap_poses].  `fill` pre-fills the doubles (ints: -77), so what
+    the kernel leaves unwritten can be told."""
+
+    def __init__(self, packed, poses=True, fill=0.0):
+        B = packed.batch
+        ifill = 0 if fill == 0.0 else -77
+        self.status = np.full(B, ifill, np.int32)
+        self.flags = np.full(B, ifill, np.int32)
+        self.metrics = np.full((B, CLR_NMETRIC), fill)
+        self.worst = np.full((B, 4), ifill, np.int32)
+        self.pose_clearance = np.full((B, packed.cap_poses), fill) if poses else None
+
+    def struct(self, ptrs=None):
+        p = ptrs or {}
+
+        def g(name):
+            a = getattr(self, name)
+            return p.get(name, None if a is None else a.ctypes.data)
+        return ClrResult(g("status"), g("flags"), g("metrics"), g("worst"), g("pose_clearance"))
+
+    def metric(self, name):
+        return self.metrics[:, CLR_METRICS.index(name)]
+
+    def flag_names(self, k):
+        return [n for n, bit in CLR_FLAGS.items() if int(self.flags[k]) & bit]
+
+    def as_dict(self, k):
+        d = {"status": CLR_STATUS[int(self.status[k])], "flags": self.flag_names(k),
+             "worst": dict(zip(("pose", "substep", "obstacle", "body"), (int(v) for v in self.worst[k])))}
+        d.update({n: float(self.metrics[k, j]) for j, n in enumerate(CLR_METRICS)})
+        return d
+
+
+def select_flag_mask(names, table):
+    """A mask of `table` (SPD_FLAGS / CLR_FLAGS) bits from flag names, or the int itself."""
+    if isinstance(names, (int, np.integer)):
+        return int(names)
+    return int(sum(table[n] for n in names))
+
+
+class SelectResults:
+    """verdict [B, C] (SEL_VERDICT bits; 0: admissible), winner [B] (-1: none), score [B] (the winner's T or NaN),
+    clearance [B]; with cap_rows > 0 out_rows [B, cap_rows, 10] and out_count [B]."""
+
+    def __init__(self, batch, C, cap_rows=0, clearance=True, fill=0.0):
+        ifill = 0 if fill == 0.0 else -77
+        self.batch, self.C, self.cap_rows = int(batch), int(C), int(cap_rows)
+        self.verdict = np.full((self.batch, self.C), ifill, np.int32)
+        self.winner = np.full(self.batch, ifill, np.int32)
+        self.score = np.full(self.batch, fill)
+        self.clearance = np.full(self.batch, fill) if clearance else None
+        self.out_rows = np.full((self.batch, self.cap_rows, len(TIMELINE_COLUMNS)), fill) if cap_rows else None
+        self.out_count = np.full(self.batch, ifill, np.int32) if cap_rows else None
+
+    def struct(self, ptrs=None):
+        p = ptrs or {}
+
+        def g(name):
+            a = getattr(self, name)
+            return p.get(name, None if a is None else a.ctypes.data)
+        return SelResult(g("verdict"), g("winner"), g("score"), g("clearance"), g("out_rows"), g("out_count"))
+
+    def flag_names(self, b, c):
+        return [n for n, bit in SEL_VERDICT.items() if int(self.verdict[b, c]) & bit]
+
+    def rows(self, b):
+        """The copied rows of problem b's winner."""
+        return self.out_rows[b, :min(int(self.out_count[b]), self.cap_rows)].copy()
+
+
+def select_in(batch, C, ptr, cap_rows=0, reject_speed_flags=0, reject_clear_flags=0, t_max=0.0):
+    """htp_select_in over the pointers `ptr` (name -> address; rows / count / clr_metrics optional)."""
+    return SelIn(int(batch), int(C), ptr["spd_status"], ptr["spd_flags"], ptr["spd_summary"], ptr.get("rows"),
+                 ptr.get("count"), int(cap_rows) if ptr.get("rows") else 0, ptr["clr_status"], ptr["clr_flags"],
+                 ptr.get("clr_metrics"), select_flag_mask(reject_speed_flags, SPD_FLAGS),
+                 select_flag_mask(reject_clear_flags, CLR_FLAGS), float(t_max))
+
+
 class ChainBatch(ctypes.Structure):  # htp_chain_batch
     _fields_ = [("batch", ctypes.c_int32), ("N", ctypes.c_int32), ("M", ctypes.c_int32),
                 ("scenes", OgeBatch), ("turns", CtBatch), ("margin", ctypes.c_void_p),
@@ -1991,6 +2208,69 @@ class Context:
 
     def speed_profile_last_ms(self):
         return self.lib.htp_speed_profile_last_ms(self.ctx)
+
+    def pose_clearance(self, packed, poses=True, out=None):
+        """Batched clearance of pose sequences against their scenes (host buffers) -> ClearResults.  `out`: a
+        ClearResults to fill; what the kernel leaves unwritten stays as it was."""
+        r = ClearResults(packed, poses) if out is None else out
+        b, rs = packed.struct(), r.struct()
+        if self.lib.htp_pose_clearance_batch(self.ctx, ctypes.byref(b), ctypes.byref(rs)) != 0:
+            raise RuntimeError(f"[htp] htp_pose_clearance_batch failed: {self.error()}")
+        return r
+
+    def pose_clearance_device(self, packed, dev_ptrs, out_ptrs, stream=None):
+        """Device-resident clearance on `stream`, not synchronised.  dev_ptrs: device pointers of poses, n_poses, obs_A,
+        obs_b, body_G, body_g and optionally pose_status, scene and margin (e.g. the buffers
+        htp_classic_turn_batch_device filled on the same stream); out_ptrs: those of the ClearResults arrays
+        (pose_clearance optional)."""
+        for k in ("poses", "n_poses") + CLR_SCENE_ARRAYS:
+            if k not in dev_ptrs:
+                raise KeyError(f"[htp] pose_clearance_device: the device pointer of {k!r} is missing")
+        b, r = packed.struct(dev_ptrs), ClrResult()
+        for k in ("pose_status", "scene", "margin"):
+            if k not in dev_ptrs:
+                setattr(b, k, None)
+        for k, v in out_ptrs.items():
+            setattr(r, k, v)
+        if self.lib.htp_pose_clearance_batch_device(self.ctx, ctypes.byref(b), ctypes.byref(r), stream) != 0:
+            raise RuntimeError(f"[htp] htp_pose_clearance_batch_device failed: {self.error()}")
+
+    def pose_clearance_last_ms(self):
+        return self.lib.htp_pose_clearance_last_ms(self.ctx)
+
+    def turn_select(self, speed, clear, C, reject_speed_flags=0, reject_clear_flags=0, t_max=0.0, rows=True, out=None):
+        """The fastest admissible candidate per problem (host buffers) -> SelectResults.  speed: a SpeedResults and
+        clear: a ClearResults of C * B paths, candidate c of problem b at index c B + b; reject_*_flags: a mask or a
+        list of SPD_FLAGS / CLR_FLAGS names; rows: copy the winner's fixed-period rows when `speed` has them."""
+        N = len(speed.status)
+        if N % int(C) or len(clear.status) != N:
+            raise ValueError("[htp] turn_select: speed and clear must hold C * B paths each")
+        B = N // int(C)
+        with_rows = bool(rows) and speed.rows is not None
+        r = SelectResults(B, C, speed.cap_rows if with_rows else 0) if out is None else out
+        ptr = {"spd_status": speed.status.ctypes.data, "spd_flags": speed.flags.ctypes.data,
+               "spd_summary": speed.summary.ctypes.data, "clr_status": clear.status.ctypes.data,
+               "clr_flags": clear.flags.ctypes.data, "clr_metrics": clear.metrics.ctypes.data}
+        if with_rows:
+            ptr.update(rows=speed.rows.ctypes.data, count=speed.count.ctypes.data)
+        b, rs = select_in(B, C, ptr, speed.cap_rows, reject_speed_flags, reject_clear_flags, t_max), r.struct()
+        if self.lib.htp_turn_select_batch(self.ctx, ctypes.byref(b), ctypes.byref(rs)) != 0:
+            raise RuntimeError(f"[htp] htp_turn_select_batch failed: {self.error()}")
+        return r
+
+    def turn_select_device(self, batch, C, dev_ptrs, out_ptrs, cap_rows=0, reject_speed_flags=0, reject_clear_flags=0,
+                           t_max=0.0, stream=None):
+        """Device-resident selection on `stream`, not synchronised.  dev_ptrs: device pointers of spd_status, spd_flags,
+        spd_summary, clr_status, clr_flags and optionally clr_metrics, rows and count (with cap_rows); out_ptrs: those
+        of the SelectResults arrays."""
+        b, r = select_in(batch, C, dev_ptrs, cap_rows, reject_speed_flags, reject_clear_flags, t_max), SelResult()
+        for k, v in out_ptrs.items():
+            setattr(r, k, v)
+        if self.lib.htp_turn_select_batch_device(self.ctx, ctypes.byref(b), ctypes.byref(r), stream) != 0:
+            raise RuntimeError(f"[htp] htp_turn_select_batch_device failed: {self.error()}")
+
+    def turn_select_last_ms(self):
+        return self.lib.htp_turn_select_last_ms(self.ctx)
 
     def oge_obstacles(self, packed, halfspaces=True):
         """Batched orchard scene -> OBCA obstacle polygons (+ halfspaces), host buffers -> OgeResults."""

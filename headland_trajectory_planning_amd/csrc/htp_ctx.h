@@ -104,6 +104,10 @@ struct htp_ctx {
   htp_event_pair speed_ev;
   htp_device_buffer speed_ws;
   int speed_groups = 0;    // workgroups of the kernel resident at once (0: not yet asked)
+  // pose clearance and turn selection (htp_clear.hip)
+  htp_event_pair clear_ev, select_ev;
+  int clear_groups = 0, select_groups = 0;   // workgroups of each kernel resident at once (0: not yet asked)
+  htp_device_buffer clear_stage;             // device copies of the host-pointer entries' arrays, kept and grown
 };
 
 static inline int fail(htp_ctx* c, const std::string& m) {

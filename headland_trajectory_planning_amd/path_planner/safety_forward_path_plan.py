@@ -615,3 +615,186 @@ def speed_profile_batch(paths, car, device=None, dt=0.0, cap_rows=None, status=N
     packed = _native.SpeedPacked(paths, [speed_limits(car, **limits)] * len(paths), dt=dt, cap_rows=cap_rows,
                                  status=status)
     return ctx.speed_profile(packed)
+
+
+# ------------------------------------------------------------------ clearance of a pose sequence, best classic turn
+def _polygon_vertices(poly):
+    """Counter-clockwise vertices of a convex polygon given as vertices [m, 2] or as halfspaces (A [e, 2], b [e]) with
+    rows of any order, possibly redundant -> [m, 2], or None when the halfspaces are empty, unbounded or degenerate."""
+    if not isinstance(poly, tuple):
+        v = np.asarray(poly, dtype=np.float64).reshape(-1, 2)
+        d, e = np.roll(v, -1, axis=0) - v, np.roll(v, -2, axis=0) - np.roll(v, -1, axis=0)
+        return v if np.sum(d[:, 0] * e[:, 1] - d[:, 1] * e[:, 0]) > 0 else v[::-1].copy()
+    A, b = np.asarray(poly[0], dtype=np.float64).reshape(-1, 2), np.asarray(poly[1], dtype=np.float64).reshape(-1)
+    nrm = np.hypot(A[:, 0], A[:, 1])
+    if not np.all(nrm > 0.0):
+        return None
+    A, b = A / nrm[:, None], b / nrm
+    ang = np.sort(np.arctan2(A[:, 1], A[:, 0]))
+    if len(ang) < 3 or np.max(np.diff(np.concatenate([ang, ang[:1] + 2.0 * math.pi]))) >= math.pi - 1e-9:
+        return None                                   # the normals leave a half plane open: unbounded (or empty)
+    pts = []
+    for i in range(len(b)):
+        for j in range(i + 1, len(b)):
+            det = A[i, 0] * A[j, 1] - A[i, 1] * A[j, 0]
+            if abs(det) <= 1e-12:
+                continue
+            p = np.array([(b[i] * A[j, 1] - b[j] * A[i, 1]) / det, (A[i, 0] * b[j] - A[j, 0] * b[i]) / det])
+            if np.all(A @ p <= b + 1e-9) and not any(np.hypot(*(p - q)) <= 1e-9 for q in pts):
+                pts.append(p)
+    if len(pts) < 3:
+        return None
+    pts = np.array(pts)
+    c = pts.mean(axis=0)
+    return pts[np.argsort(np.arctan2(pts[:, 1] - c[1], pts[:, 0] - c[0]))]
+
+
+def _polygon_signed_distance(P, Q):
+    """Signed distance of two convex counter-clockwise polygons: the largest, over the edge normals of both, of the
+    least projection gap; when that is positive they are disjoint and the distance is the least vertex-to-edge
+    distance over both directions, otherwise it is minus the penetration depth."""
+    sep, d2 = -math.inf, math.inf
+    for F, V in ((P, Q), (Q, P)):
+        e = np.roll(F, -1, axis=0) - F
+        ln = np.hypot(e[:, 0], e[:, 1])
+        u = e / ln[:, None]
+        nrm = np.stack([u[:, 1], -u[:, 0]], axis=1)       # outward normals of a counter-clockwise polygon
+        w = V[None, :, :] - F[:, None, :]                 # [edge, vertex, 2]
+        pr = np.einsum("evk,ek->ev", w, nrm)
+        al = np.einsum("evk,ek->ev", w, u)
+        ex = np.maximum(np.maximum(-al, al - ln[:, None]), 0.0)
+        sep = max(sep, float(np.max(np.min(pr, axis=1))))
+        d2 = min(d2, float(np.min(pr * pr + ex * ex)))
+    return math.sqrt(d2) if sep > 0.0 else sep
+
+
+def pose_clearance(poses, obstacles, bodies, substeps=1, margin=None, libm=None, margin_tol=0.0):
+    """The clearance of one pose sequence (rows x, y, yaw) against obstacle polygons, with the body polygons placed at
+    every pose, as include/htp.h defines it ("Clearance of pose sequences"), in plain numpy: the statement the batched
+    kernel is tested against.  obstacles / bodies: lists of vertices [m, 2] or of halfspaces (A, b).  Returns a dict:
+    status ("ok" / "bad_input" / "bad_polytope"), clearance, clearance_node, max_gap, max_turn, worst (pose, substep,
+    obstacle, body), pose_clearance [n], flags (set of "collision", "margin"), runner_up (test support: the least
+    signed distance of an item that is greater than the clearance, i.e. how far `worst` is from a tie, so that the tests
+    can draw scenes whose `worst` is decidable).  margin_tol is the kernel's option of that name.  `libm`: an object with sin, cos and
+    hypot (default: math); the tests pass the project's correctly rounded ones, which the kernel uses."""
+    lm = math if libm is None else libm
+    P = np.asarray(poses, dtype=np.float64)
+    S = int(substeps)
+    if P.ndim != 2 or P.shape[0] < 1 or P.shape[1] < 3 or not np.all(np.isfinite(P[:, :3])):
+        return dict(status="bad_input", flags=set())
+    if margin is not None and not math.isfinite(margin):
+        return dict(status="bad_input", flags=set())
+    for poly in list(obstacles) + list(bodies):
+        if isinstance(poly, tuple) and not (np.all(np.isfinite(poly[0])) and np.all(np.isfinite(poly[1]))):
+            return dict(status="bad_input", flags=set())
+    obs = [_polygon_vertices(o) for o in obstacles]
+    bod = [_polygon_vertices(o) for o in bodies]
+    if any(o is None for o in obs + bod):
+        return dict(status="bad_polytope", flags=set())
+    n = len(P)
+    x, y, yaw = P[:, 0], P[:, 1], P[:, 2]
+    best, node, worst = math.inf, math.inf, None
+    gap = turn = 0.0
+    per_pose = np.full(n, math.inf)
+    every = []
+    for i in range(n):
+        dx = dy = dw = 0.0
+        if i < n - 1:
+            dx, dy, d = x[i + 1] - x[i], y[i + 1] - y[i], yaw[i + 1] - yaw[i]
+            dw = d - 2.0 * math.pi * math.floor((d + math.pi) / (2.0 * math.pi))
+            gap = max(gap, lm.hypot(dx, dy))
+            turn = max(turn, abs(dw))
+        for q in range(S if i < n - 1 else 1):
+            lam = float(q) / float(S)
+            px, py, pw = (x[i] + lam * dx, y[i] + lam * dy, yaw[i] + lam * dw) if q else (x[i], y[i], yaw[i])
+            cs, sn = lm.cos(pw), lm.sin(pw)
+            R = np.array([[cs, sn], [-sn, cs]])
+            for m, O in enumerate(obs):
+                for k, Bk in enumerate(bod):
+                    d = _polygon_signed_distance(O, Bk @ R + [px, py])
+                    every.append(d)
+                    if d < best:
+                        best, worst = d, (i, q, m, k)
+                    if q == 0:
+                        node = min(node, d)
+                    per_pose[i] = min(per_pose[i], d)
+    flags = set()
+    if best < 0.0:
+        flags.add("collision")
+    if margin is not None and best < margin - margin_tol:
+        flags.add("margin")
+    return dict(status="ok", clearance=best, clearance_node=node, max_gap=gap, max_turn=turn, worst=worst,
+                pose_clearance=per_pose, flags=flags, runner_up=min([v for v in every if v > best], default=math.inf))
+
+
+def classic_turn_portfolio(packed, turns, car, types=("dubins", "circleback", "fishtail"), device=None, dt=0.1,
+                           cap_rows=None, substeps=2, reject_steer_exceeds=True, cap_path=1024, **limits):
+    """Per headland, the fastest classic turn that clears the obstacle set the solve is held to.  `packed`: the
+    _native.PackedBatch the solve takes (its obstacles, bodies and min_dist as margin); `turns`: one ClassicPacked dict
+    per problem (synth.classic_turn(meta)); every problem is planned as each of `types`: all C B turns in one
+    htp_classic_turn_batch_device launch (candidate c of problem b at index c B + b), then the speed profile, the
+    clearance of the planner's paths and the selection behind it on the same stream, with no host round trip between
+    the launches.  A candidate that collides or misses the margin is rejected, and one that exceeds the steering bound
+    unless reject_steer_exceeds is off; `limits` as speed_profile.  Returns a dict: types, winner [B] (index into
+    types, -1: none), winner_type [B], T [B], clearance [B], rows (list of [count][10]), verdict [B, C], and per
+    candidate [C, B] T_all, clearance_all, speed_status, clear_status, clear_flags, speed_flags; select is the
+    _native.SelectResults behind winner, T, clearance and rows.  cap_path: rows of storage per planned turn."""
+    import torch
+
+    from .. import _native as N_
+    ctx = device if isinstance(device, N_.Context) else N_.Context(0 if device is None else int(device))
+    B, C = packed.batch, len(types)
+    if len(turns) != B:
+        raise ValueError("classic_turn_portfolio: one turn per problem of the batch")
+    dev = torch.device("cuda", ctx.device)
+    ck = N_.ClassicPacked([dict(t, type=typ) for typ in types for t in turns], cap_path=cap_path)
+    sk = N_.SpeedPacked.resident(C * B, ck.cap_path, speed_limits(car, **limits), dt=dt, cap_rows=cap_rows)
+    lk = N_.ClearPacked.resident(C * B, ck.cap_path, (packed.obs_edges, packed.body_edges), B,
+                                 substeps=substeps, **N_.CLR_PATH_LAYOUT)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+    t_in = {k: up(getattr(ck, k)) for k in ("params", "desc", "poly_off", "vertices")}
+    t_sc = {k: up(getattr(packed, k)) for k in N_.CLR_SCENE_ARRAYS}
+    t_sc.update(limits=up(sk.limits), scene=up(np.tile(np.arange(B, dtype=np.int32), C)),
+                margin=up(packed.params[:, N_.P_DMIN]))
+    z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)   # noqa: E731
+    i32 = torch.int32
+    t_turn = {"status": z(C * B, dtype=i32), "n_path": z(C * B, dtype=i32), "path": z(C * B, ck.cap_path, 5)}
+    t_spd = {"status": z(C * B, dtype=i32), "flags": z(C * B, dtype=i32), "summary": z(C * B, N_.SPD_NSUM),
+             "count": z(C * B, dtype=i32)}
+    if sk.dt > 0.0:
+        t_spd["rows"] = z(C * B, sk.cap_rows, 10)
+    t_clr = {"status": z(C * B, dtype=i32), "flags": z(C * B, dtype=i32), "metrics": z(C * B, N_.CLR_NMETRIC),
+             "worst": z(C * B, 4, dtype=i32)}
+    sel = N_.SelectResults(B, C, sk.cap_rows if sk.dt > 0.0 else 0)
+    t_sel = {k: up(getattr(sel, k)) for k in ("verdict", "winner", "score", "clearance", "out_rows", "out_count")
+             if getattr(sel, k) is not None}
+    ptr = lambda d: {k: v.data_ptr() for k, v in d.items()}   # noqa: E731
+    stream = torch.cuda.Stream(dev)
+    s = stream.cuda_stream
+    ctx.classic_turns_device(ck, ptr(t_in), ptr(t_turn), stream=s)
+    ctx.speed_profile_device(sk, {"path": t_turn["path"].data_ptr(), "n_path": t_turn["n_path"].data_ptr(),
+                                  "path_status": t_turn["status"].data_ptr(), "limits": t_sc["limits"].data_ptr()},
+                             ptr(t_spd), stream=s)
+    ctx.pose_clearance_device(lk, dict(ptr({k: t_sc[k] for k in N_.CLR_SCENE_ARRAYS + ("scene", "margin")}),
+                                       poses=t_turn["path"].data_ptr(), n_poses=t_turn["n_path"].data_ptr(),
+                                       pose_status=t_turn["status"].data_ptr()), ptr(t_clr), stream=s)
+    sp = {"spd_status": t_spd["status"], "spd_flags": t_spd["flags"], "spd_summary": t_spd["summary"],
+          "clr_status": t_clr["status"], "clr_flags": t_clr["flags"], "clr_metrics": t_clr["metrics"]}
+    if sk.dt > 0.0:
+        sp.update(rows=t_spd["rows"], count=t_spd["count"])
+    ctx.turn_select_device(B, C, ptr(sp), ptr(t_sel), cap_rows=sk.cap_rows,
+                           reject_speed_flags=["STEER_EXCEEDS"] if reject_steer_exceeds else 0,
+                           reject_clear_flags=["COLLISION", "MARGIN"], stream=s)
+    stream.synchronize()
+    for k, v in t_sel.items():
+        getattr(sel, k)[...] = v.cpu().numpy()
+    host = lambda t: t.cpu().numpy().reshape((C, B) + tuple(t.shape[1:]))   # noqa: E731
+    spd_status, summary = host(t_spd["status"]), host(t_spd["summary"])
+    clr_status, metrics = host(t_clr["status"]), host(t_clr["metrics"])
+    T_all = np.where(spd_status == N_.SPD_OK, summary[:, :, 0], np.nan)
+    c_all = np.where(clr_status == N_.CLR_OK, metrics[:, :, 0], np.nan)
+    return dict(types=tuple(types), winner=sel.winner, winner_type=[types[w] if w >= 0 else None for w in sel.winner],
+                T=sel.score, clearance=sel.clearance, rows=[sel.rows(b) for b in range(B)] if sk.dt > 0.0 else None,
+                verdict=sel.verdict, T_all=T_all, clearance_all=c_all, speed_status=spd_status,
+                clear_status=clr_status, clear_flags=host(t_clr["flags"]), speed_flags=host(t_spd["flags"]),
+                select=sel)

@@ -1249,6 +1249,123 @@ int htp_speed_profile_batch_device(htp_ctx* ctx, const htp_speed_in* in, htp_spe
 double htp_speed_profile_last_ms(htp_ctx* ctx);
 
 /* ---------------------------------------------------------------------------
+ * Clearance of pose sequences against OBCA polytopes, and the fastest admissible candidate per headland (no reference
+ * counterpart: the classic planners there ignore the obstacle set the solve is held to; csrc/clear_core.h, DESIGN.md
+ * s.3.18).  One wavefront per path, workgroups stride over the batch.
+ *
+ * Input per path p: rows poses[p][cap_poses][stride] with a launch-uniform stride >= 3 and the columns col_x, col_y,
+ *   col_yaw (distinct, < stride): planner paths [x, y, yaw, k, dir] are stride 5, columns (0, 1, 2); fixed-period rows
+ *   of either kind of turn are stride HTP_TIMELINE_NCOL, columns (1, 2, 4).  n = min(n_poses[p], cap_poses) poses are
+ *   used and HTP_CLR_F_TRUNCATED is set when n_poses[p] > cap_poses, so htp_speed_result.count can be passed straight
+ *   in.  A non-zero pose_status entry ends the path HTP_CLR_SKIPPED, so htp_classic_result.status or the speed status
+ *   goes straight in.  scene[p] (nullable: scene[p] = p, which requires n_scenes == batch) names the obstacle / body
+ *   set of the path, so several candidate turns of one headland share one set.
+ * Scenes: n_scenes sets of M <= 16 obstacles and K <= 4 bodies as halfspaces in the layout of htp_obca_batch: obs_A,
+ *   obs_b, body_G, body_g indexed by scene (obs_edges / body_edges are host arrays, launch-uniform, 3..8 each), turned
+ *   into edges by the audit's rule (rows of any order, possibly redundant); margin[n_scenes] nullable, finite, may be
+ *   negative.
+ * Poses measured: the n given poses and, with substeps S > 1, S-1 poses inside every gap i -> i+1: for q = 1..S-1,
+ *   lam = (double)q / S, x = x_i + lam (x_{i+1} - x_i), y likewise, yaw = yaw_i + lam wrap(yaw_{i+1} - yaw_i) with the
+ *   speed block's wrap(d) = d - 2 pi floor((d + pi) / (2 pi)).  The yaw column is the vehicle's heading, on reverse
+ *   segments too.  Each pose places every body (the audit's signed distance of two convex polygons: the sign is exact,
+ *   the magnitude is the distance when they are disjoint and minus the penetration depth otherwise).
+ * Outputs.  status HTP_CLR_*: BAD_INPUT is n < 1, a non-finite double among those read (the three columns of the n
+ *   poses, the scene's rows, its margin) or a scene index outside 0..n_scenes-1; BAD_POLYTOPE is an empty or unbounded
+ *   obstacle or body.  flags HTP_CLR_F_*: COLLISION clearance < 0; MARGIN margin given and clearance < margin -
+ *   margin_tol; TRUNCATED.  metrics[HTP_CLR_*]: CLEARANCE the least signed distance over all poses and (obstacle, body)
+ *   pairs, CLEARANCE_NODE the same over the given poses only, MAX_GAP the largest hypot between consecutive given
+ *   poses and MAX_TURN the largest |wrap(yaw_{i+1} - yaw_i)| (both 0 for n == 1: they tell whether S was enough).
+ *   worst[4]: pose, substep, obstacle and body of CLEARANCE, ties to the lowest tuple.  pose_clearance (nullable)
+ *   [cap_poses]: the least over the pairs for pose i and the substeps of the gap it opens.  Of a path that is not
+ *   HTP_CLR_OK only status and flags = 0 are written; entries from n on are never written.
+ * Every reduction is a minimum or a maximum: the result does not depend on lane order, chunking or workgroup count. */
+#define HTP_CLR_NMETRIC 4
+#define HTP_CLR_MAX_SUBSTEPS 16
+enum { HTP_CLR_CLEARANCE = 0, HTP_CLR_CLEARANCE_NODE, HTP_CLR_MAX_GAP, HTP_CLR_MAX_TURN };
+enum { HTP_CLR_OK = 0, HTP_CLR_SKIPPED = 1, HTP_CLR_BAD_INPUT = 2, HTP_CLR_BAD_POLYTOPE = 3 };
+enum { HTP_CLR_F_COLLISION = 1, HTP_CLR_F_MARGIN = 2, HTP_CLR_F_TRUNCATED = 4 };
+typedef struct {
+  int32_t batch, cap_poses, stride, col_x, col_y, col_yaw;
+  const double* poses;         /* [batch][cap_poses][stride] */
+  const int32_t* n_poses;      /* [batch] */
+  const int32_t* pose_status;  /* nullable [batch]: non-zero -> HTP_CLR_SKIPPED */
+  const int32_t* scene;        /* nullable [batch]: the path's scene; null: scene[p] = p */
+  int32_t n_scenes, M, K;
+  const int32_t* obs_edges;    /* [M] host array, 3..8 each */
+  const int32_t* body_edges;   /* [K] host array, 3..8 each */
+  const double* obs_A;         /* [n_scenes][sum obs_edges][2] */
+  const double* obs_b;         /* [n_scenes][sum obs_edges] */
+  const double* body_G;        /* [n_scenes][sum body_edges][2] */
+  const double* body_g;        /* [n_scenes][sum body_edges] */
+  const double* margin;        /* nullable [n_scenes] */
+  int32_t substeps;            /* S, 1..HTP_CLR_MAX_SUBSTEPS */
+  double margin_tol;           /* >= 0 */
+  int32_t max_groups;          /* workgroups of the launch; 0: as many as are resident at once */
+} htp_clear_in;
+typedef struct {
+  int32_t* status;             /* [batch] HTP_CLR_* */
+  int32_t* flags;              /* [batch] HTP_CLR_F_* bits */
+  double* metrics;             /* [batch][HTP_CLR_NMETRIC] */
+  int32_t* worst;              /* [batch][4] pose, substep, obstacle, body */
+  double* pose_clearance;      /* nullable [batch][cap_poses] */
+} htp_clear_result;
+/* API errors (-1 with a "[clearance]" message, nothing launched): a null required argument, batch < 0, cap_poses < 1,
+ * a bad stride or column, M, K or an edge count out of range, n_scenes < 1, a null scene with n_scenes != batch,
+ * substeps out of range, a negative (or non-finite) tolerance, max_groups < 0, cap_poses * substeps * M * K >= 2^31
+ * (the index of the worst pose is an int32).  batch == 0 returns 0. */
+/* host pointers, synchronous; the caller's output arrays travel to the device and back, so what the kernel leaves
+ * unwritten stays as it was */
+int htp_pose_clearance_batch(htp_ctx* ctx, const htp_clear_in* in, htp_clear_result* out);
+/* device pointers (obs_edges / body_edges stay host arrays), enqueued on `stream`, not synchronised */
+int htp_pose_clearance_batch_device(htp_ctx* ctx, const htp_clear_in* in, htp_clear_result* out, void* stream);
+/* duration (ms) of the last clearance kernel (hipEvents on its stream) */
+double htp_pose_clearance_last_ms(htp_ctx* ctx);
+
+/* The fastest admissible candidate per problem.  batch B problems with C candidates each (1..8); candidate c of
+ * problem b sits at index c B + b in every input array (the layout of C B paths planned, timed and measured in one
+ * launch each).  Verdict per candidate (verdict[B][C], HTP_SEL_* bits; 0: admissible):
+ *   NOT_PLANNED  speed status HTP_SPD_SKIPPED;
+ *   BAD          speed status neither HTP_SPD_OK nor HTP_SPD_SKIPPED (HTP_SPD_BAD_INPUT), or clearance status not
+ *                HTP_CLR_OK;
+ *   SPEED_FLAG   the speed flags hit reject_speed_flags; CLEAR_FLAG the clearance flags hit reject_clear_flags;
+ *   TOO_LONG     t_max > 0 and T > t_max; NONFINITE T is not finite, where T = spd_summary[HTP_SPD_S_T] is read only
+ *                of a candidate whose speed status is HTP_SPD_OK (the speed profile writes no summary otherwise).
+ * winner[B]: the admissible candidate of least T, an equal T goes to the lowest c; -1 without one.  score[B]: its T,
+ * or NaN.  clearance[B] (nullable; needs clr_metrics): its HTP_CLR_CLEARANCE, or NaN.  With rows, the winner's first
+ * min(count, cap_rows) rows are copied to out_rows[B][cap_rows][HTP_TIMELINE_NCOL] and out_count[B] is its count (0
+ * without a winner); rows beyond that are left as they were.  One wavefront per problem; no reduction. */
+#define HTP_SEL_MAX_CAND 8
+enum { HTP_SEL_NOT_PLANNED = 1, HTP_SEL_BAD = 2, HTP_SEL_SPEED_FLAG = 4, HTP_SEL_CLEAR_FLAG = 8, HTP_SEL_TOO_LONG = 16,
+       HTP_SEL_NONFINITE = 32 };
+typedef struct {
+  int32_t batch, C;
+  const int32_t* spd_status;   /* [C][batch] */
+  const int32_t* spd_flags;    /* [C][batch] */
+  const double* spd_summary;   /* [C][batch][HTP_SPD_NSUM] */
+  const double* rows;          /* nullable [C][batch][cap_rows][HTP_TIMELINE_NCOL] */
+  const int32_t* count;        /* [C][batch]; required with rows */
+  int32_t cap_rows;            /* >= 1 with rows */
+  const int32_t* clr_status;   /* [C][batch] */
+  const int32_t* clr_flags;    /* [C][batch] */
+  const double* clr_metrics;   /* nullable [C][batch][HTP_CLR_NMETRIC] */
+  int32_t reject_speed_flags, reject_clear_flags;
+  double t_max;                /* 0: off */
+} htp_select_in;
+typedef struct {
+  int32_t* verdict;            /* [batch][C] HTP_SEL_* bits */
+  int32_t* winner;             /* [batch] */
+  double* score;               /* [batch] */
+  double* clearance;           /* nullable [batch] */
+  double* out_rows;            /* [batch][cap_rows][HTP_TIMELINE_NCOL]; required with rows */
+  int32_t* out_count;          /* [batch]; required with rows */
+} htp_select_result;
+/* API errors (-1 with a "[select]" message, nothing launched): a null required argument, batch < 0, C outside 1..8,
+ * rows without count, out_rows, out_count or cap_rows >= 1, clearance without clr_metrics, t_max negative or NaN. */
+int htp_turn_select_batch(htp_ctx* ctx, const htp_select_in* in, htp_select_result* out);
+int htp_turn_select_batch_device(htp_ctx* ctx, const htp_select_in* in, htp_select_result* out, void* stream);
+double htp_turn_select_last_ms(htp_ctx* ctx);
+
+/* ---------------------------------------------------------------------------
  * Orchard workload chain on the device (synth.make_orchard_instance's steps after the scene draws): for each
  * problem, the classic turn (htp_classic_turn_batch) -> get_init_ref_path at spacing ds / 2 = L / (2N - 2)
  * (ds = L / (N - 1), the resampled spacing), desired_v = min(ds / dT, 0.9) (R/obca_py/util.py:62-113) -> the init guess resampled to N rows and the
